@@ -12,8 +12,14 @@ max-over-ranks time.
 
 Also reported: roofline of the dominant kernel family (the MFMA implicit-GEMM
 convs of both networks: algorithmic FLOPs / HIP-event time of their launches
-inside the timed region) and a bounded CPU baseline (the oracle port of the same
-pipeline, rank 0, N=1).
+inside the timed region).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs with --dump-outputs DIR and prints the result line. --full adds what
+takes runs of its own after the timed steps: a bounded CPU baseline (the oracle
+port of the same pipeline, rank 0, N=1), the parity passes (device f32 mode,
+other precisions, CPU oracle), the HBM rates of the bandwidth-bound kernels and
+the per-workload breakdowns.
 """
 from __future__ import annotations
 
@@ -430,6 +436,29 @@ def f16_parity(fe16, devs, bank_h, conf: float = 0.5) -> dict:
                         "bench frames are u8 noise, so a sub-pixel landmark shift resamples the chip)"}}
 
 
+def _save_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: one <name>.npy per array, float32 / float64."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
+def dump_faces(path: str, res, extra: dict = None) -> None:
+    """--dump-outputs of an extract_batch result (a list of face dicts per frame): one row per face,
+    the faces of a frame ordered by box, so that two builds can be compared row by row."""
+    rows = [(i, f) for i, r in enumerate(res) for f in sorted(r, key=lambda f: tuple(int(v) for v in f["bbox"]))]
+    out = {"faces_per_frame": np.array([len(r) for r in res], np.float64),
+           "frame_index": np.array([i for i, _ in rows], np.float64),
+           "bbox": np.array([f["bbox"] for _, f in rows], np.float64).reshape(len(rows), 4),
+           "quality": np.array([f["quality"] for _, f in rows], np.float64),
+           "feat": np.array([f["feat"] for _, f in rows], np.float32).reshape(len(rows), -1)}
+    if rows and all("fd" in f for _, f in rows):
+        out["fd"] = np.array([f["fd"] for _, f in rows], np.float64)
+    out.update(extra or {})
+    _save_outputs(path, out)
+
+
 def smooth_frames(frames: np.ndarray) -> np.ndarray:
     """The bench frames low-pass filtered (Gaussian, sigma 1.5 px), contrast restored x2.5 about
     the noise mean 127.5 (camera-like images: a sub-pixel landmark shift no longer resamples the
@@ -697,8 +726,17 @@ def main():
     ap.add_argument("--c5-samples", type=int, default=1024,
                     help="C5: samples of the one clip whose positions are sharded over the ranks (strong scaling; "
                          "1024 = 128 per rank at 8 GPUs, two full speculative chunks of the default batch 64)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the f16-vs-f32 decision parity pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the CPU baseline, the "
+                         "parity passes against the device f32 mode / other precisions / the CPU oracle, the HBM rates "
+                         "of the bandwidth-bound kernels, and the breakdowns that take a step of their own (C2 flip-TTA "
+                         "and per-kernel split, C4 stage breakdown, the per-frame mode's profiled step). A plain run "
+                         "sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="--full: skip the f16-vs-f32 decision parity passes and the HBM rates")
     ap.add_argument("--precision", default="f16", choices=["f16", "f32", "f16x3", "f16c8"],
                     help="c3/c4/c5: f16 = the timed mode (SCRFD and ArcFace f16x3 by default, DESIGN.md §3.6-3.7), "
                          "f32 = the f32 parity mode; c2: the ArcFace program's precision (f16 = BASELINE C2's fp16, "
@@ -811,12 +849,15 @@ def main():
     ctx.sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        res = step()
     ctx.sync()
     t1 = time.perf_counter()
     _barrier(world)
     elapsed = _max_over_ranks(world, t1 - t0)
-    if not prof_timed and not os.getenv("PC_BENCH_NOPROF"):
+    if args.dump_outputs and rank == 0:
+        dump_faces(args.dump_outputs, res)
+    prof_after = args.full and not prof_timed and not os.getenv("PC_BENCH_NOPROF")
+    if prof_after:
         for n in nets:
             n.profile(True)
         step()
@@ -891,7 +932,8 @@ def main():
                                      "launch's duration includes the co-running kernels' share of the CUs",
                      "per_net": {name: _net_roof(name, p_, prof_steps, fe) for name, p_ in zip(net_names, prof)},
                      "events": ("HIP events over the timed region" if prof_timed else
-                                "HIP events of one profiled step after the timed region (its timed steps replay HIP graphs)"),
+                                "HIP events of one profiled step after the timed region (its timed steps replay HIP graphs)"
+                                if prof_after else "none (--full adds one profiled step after the timed region)"),
                      "traffic_unit": "HBM bytes per launch of the dominant kernel (rocprofv3 FETCH_SIZE x2 + "
                                      "WRITE_SIZE, bench_traffic.json); conv_family.traffic_mean_per_launch: the mean "
                                      "over all conv launches",
@@ -899,7 +941,7 @@ def main():
         "cpu_baseline": None,
     }
     res32 = res16 = None
-    if rank == 0 and args.precision == "f16" and not args.no_parity and args.frames == "resident" and \
+    if rank == 0 and args.full and args.precision == "f16" and not args.no_parity and args.frames == "resident" and \
             fe.detector_backend == "scrfd":
         out["parity"] = f16_parity(fe, devs, bank_h)
         res32, res16 = out["parity"].pop("_res32"), out["parity"].pop("_res16")
@@ -949,9 +991,9 @@ def main():
         out["parity"]["timed_mode_speedup_vs_detector_f32_mode"] = round(
             value / out["parity"]["detector_f32_mode"]["frames_per_s"], 3)
         out["parity"]["smooth_frames"] = smooth_parity(fe, frames, args.bank)
-    if rank == 0 and args.frames == "resident" and not args.no_parity:
+    if rank == 0 and args.full and args.frames == "resident" and not args.no_parity:
         out["hbm"] = hbm_kernels(fe, devs, 1080, 1920)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(frames, fe, bank_h, args.cpu_sample, args.cpu_sample_1t)
         oracle_res = out["cpu_baseline"].pop("_oracle_results")
         if res16 is not None:
@@ -1006,16 +1048,21 @@ def main_c2(args):
     d_out = ctx.alloc(B * eng.dim * 4)
     for _ in range(max(1, args.warmup)):
         eng.embed_device(d_chips.ptr, B, False, d_out.ptr)
-        eng.embed_device(d_chips.ptr, B, True, d_out.ptr)
+        if args.full:
+            eng.embed_device(d_chips.ptr, B, True, d_out.ptr)
     ctx.sync()
     elapsed, _ = _timed(world, ctx, args.steps, lambda: eng.embed_device(d_chips.ptr, B, False, d_out.ptr))
-    t_flip, _ = _timed(world, ctx, args.steps, lambda: eng.embed_device(d_chips.ptr, B, True, d_out.ptr))
-    # per-launch split of one profiled step (HIP events on the net's stream)
-    eng.net.profile(True)
-    eng.embed_device(d_chips.ptr, B, False, d_out.ptr)
-    dom = dominant_conv([eng.net], ("arcface",), [eng.program], {"arcface": args.precision})
-    recs = eng.net.profile_ops()
-    eng.net.profile(False)
+    if args.dump_outputs and rank == 0:
+        _save_outputs(args.dump_outputs, {"embeddings": ctx.download(d_out.ptr, (B, eng.dim), np.float32)})
+    dom, recs, t_flip = None, [], None
+    if args.full:
+        t_flip, _ = _timed(world, ctx, args.steps, lambda: eng.embed_device(d_chips.ptr, B, True, d_out.ptr))
+        # per-launch split of one profiled step (HIP events on the net's stream)
+        eng.net.profile(True)
+        eng.embed_device(d_chips.ptr, B, False, d_out.ptr)
+        dom = dominant_conv([eng.net], ("arcface",), [eng.program], {"arcface": args.precision})
+        recs = eng.net.profile_ops()
+        eng.net.profile(False)
     # algorithmic FLOPs over the dense f16 peak for every f16-MFMA form (f16x3 / f16c8 issue 3x / 1.5x
     # that work: issued_mfma_frac)
     peak = _peak_for(args.precision)
@@ -1046,12 +1093,14 @@ def main_c2(args):
                      "per_kernel": {k: {"launches": v[0], "ms": round(v[1], 4),
                                         "tflops": round(v[2] / (v[1] * 1e-3) / 1e12, 1) if v[1] > 0 and v[2] > 0
                                         else None} for k, v in sorted(split.items(), key=lambda kv: -kv[1][1])}},
-        "flip_tta": {"faces_per_step": B, "rows": 2 * B, "ms_per_step": round(t_flip / args.steps * 1e3, 4),
-                     "faces_per_s": round(_sum_over_ranks(world, B * args.steps) / t_flip, 2),
-                     "tflops": round(2 * fl / (t_flip / args.steps) / 1e12, 2)},
+        "flip_tta": None,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full:
+        out["flip_tta"] = {"faces_per_step": B, "rows": 2 * B, "ms_per_step": round(t_flip / args.steps * 1e3, 4),
+                           "faces_per_s": round(_sum_over_ranks(world, B * args.steps) / t_flip, 2),
+                           "tflops": round(2 * fl / (t_flip / args.steps) / 1e12, 2)}
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_c2(arc_params, chips, 16)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -1112,6 +1161,7 @@ def main_other(args):
     bank_h = synth_bank(bank_n)
     bank = DeviceBank(ctx, bank_h)
     stats = {}
+    last = {}   # what the last step returned (--dump-outputs)
     nets = [fe._arc.net]
     units_per_step = args.batch
     scaling = "weak"
@@ -1204,6 +1254,7 @@ def main_other(args):
             stats["persons"] = len(crops)
             stats["faces"] = sum(len(f) for f in faces)
             stats["faces_per_crop"] = round(stats["faces"] / max(1, len(crops)), 3)
+            last["faces"] = faces
             return feats
         nets += [fe._engine(640).net, reid._engine.net]
         wl = (f"C4: YOLOv8n persons + SCRFD-10G@640 per person crop + ArcFace-R100 flip-TTA + CLIP ViT-L/14 ReID "
@@ -1260,11 +1311,22 @@ def main_other(args):
         nets += [e.net for e in fe._scrfd_engines.values()]
     for n in nets:
         n.profile(True)
-    elapsed, local_dt = _timed(world, ctx, args.steps, step)
+    def timed_step():
+        last["out"] = step()
+    elapsed, local_dt = _timed(world, ctx, args.steps, timed_step)
+    if args.dump_outputs and rank == 0:
+        if c4:
+            dump_faces(args.dump_outputs, last["faces"], {"reid_feat": np.asarray(last["out"], np.float32)})
+        else:
+            spans, grown, recs, _ = last["out"]
+            _save_outputs(args.dump_outputs, {
+                "spans": np.asarray(spans, np.float64).reshape(-1, 2),
+                "bank": np.asarray(grown, np.float32),
+                "records": np.array([[x.idx, x.extracted, x.best, x.n_faces, x.active] for x in recs], np.float64)})
     prof = [n.profile_read() for n in nets]
     for n in nets:
         n.profile(False)
-    if c4:
+    if c4 and args.full:
         # where a C4 step goes: one more step, stage by stage with the device drained
         # between stages (so the stages do not overlap here as they may in the timed steps), with the
         # FaceEmbedder's host phase timers on
@@ -1325,9 +1387,9 @@ def main_other(args):
                      "conv_share_of_step": round(conv_ms * 1e-3 / local_dt, 4), "per_net": per_net},
         "cpu_baseline": None,
     }
-    if rank == 0 and not c4 and not args.no_parity:
+    if rank == 0 and not c4 and args.full and not args.no_parity:
         out["hbm"] = hbm_kernels(fe, devs, H, W, kinds=("resize_area",))
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         print(f"[bench {args.workload}] CPU baseline (oracle port) ...", file=sys.stderr, flush=True)
         out["cpu_baseline"] = cpu_baseline_c4(frames, fe, det, bank_h) if c4 else \
             cpu_baseline_c5(frames, fe, bank_h, stride)

@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import bench
+from golden_parts import load_golden
 from oracle import cv_ops
 from oracle import nets_torch as nt
 from oracle import pipeline as op
@@ -311,7 +312,7 @@ def test_c2_arcface_batch256(gpu_ctx, prec, tol):
 def test_bank_match_on_fd_min_goldens(gpu_ctx):
     """pc_bank_match vs the reference's own _fd_min outputs (tools/gen_golden.py): the dot
     products are summed in a different order than numpy's sgemv, so 1e-6."""
-    d = np.load(os.path.join(G, "fd_min.npz"), allow_pickle=False)
+    d = load_golden(os.path.join(G, "fd_min.npz"))
     feats = np.ascontiguousarray(d["feats"], np.float32)
     dq = gpu_ctx.upload(feats)
     fd = gpu_ctx.alloc(4 * len(feats))

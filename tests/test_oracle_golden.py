@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from golden_parts import load_golden
 from oracle import ref_algos as ra
 from person_capture_amd import imageops, match
 
@@ -15,7 +16,7 @@ G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _load(name):
-    return np.load(os.path.join(G, name), allow_pickle=False)
+    return load_golden(os.path.join(G, name))
 
 
 @pytest.mark.parametrize("impl", [ra.fd_min, match.fd_min])

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from golden_parts import load_golden
 from person_capture_amd import postmatch as pm
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "postmatch.npz")
@@ -15,7 +16,7 @@ RATIOS = ["2:3", "16:9", "1:1", "4:5"]
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(G, allow_pickle=False)
+    return load_golden(G)
 
 
 def test_enforce_scale_and_margins(gold):

@@ -69,6 +69,15 @@ class _Cfg:
         self.__dict__.update(kw)
 
 
+def _savez_parts(path, first, *parts):
+    """A set too large for one committed file: `first` goes to <stem>.npz, every further dict to
+    <stem>.part<k>.npz (tests/golden_parts.load_golden joins them; an array cut along axis 0
+    keeps its name in every part)."""
+    np.savez_compressed(path, **first)
+    for k, p in enumerate(parts):
+        np.savez_compressed(path[:-len(".npz")] + f".part{k}.npz", **p)
+
+
 def main():
     _stub_cv2()
     sys.path.insert(0, REF)
@@ -94,9 +103,10 @@ def main():
     fd_edge = np.array([P._fd_min(None, banks[0]), P._fd_min(feats[0], None),
                         P._fd_min(feats[0], np.zeros((0, 512), np.float32)),
                         P._fd_min(feats[0], banks[0][0])], np.float64)
-    np.savez_compressed(os.path.join(OUT, "fd_min.npz"), feats=np.stack(feats),
-                        bank_sizes=np.array([b.shape[0] for b in banks]),
-                        banks=np.concatenate(banks, 0), fd=np.array(fds, np.float64), fd_edge=fd_edge)
+    _savez_parts(os.path.join(OUT, "fd_min.npz"),
+                 dict(feats=np.stack(feats), bank_sizes=np.array([b.shape[0] for b in banks]),
+                      fd=np.array(fds, np.float64), fd_edge=fd_edge),
+                 *[dict(banks=c) for c in np.array_split(np.concatenate(banks, 0), 3)])
 
     # ---- _stream_ref_bank_update action sequences ----
     seqs = {}
@@ -238,10 +248,11 @@ def main():
         thr = [10, 5, 20][t % 3]
         borders.append(img)
         bb_out.append(list(U.detect_black_borders(img, thr=thr)) + [thr])
-    np.savez_compressed(os.path.join(OUT, "postmatch.npz"), esm_in=np.array(esm_in, np.float64),
-                        esm_out=np.array(esm_out, np.int64), clip_in=np.array(clip_in, np.float64),
-                        clip_out=np.array(clip_out, np.int64), bb_out=np.array(bb_out, np.int64),
-                        **{f"border{i}": b for i, b in enumerate(borders)})
+    _savez_parts(os.path.join(OUT, "postmatch.npz"),
+                 dict(esm_in=np.array(esm_in, np.float64), esm_out=np.array(esm_out, np.int64),
+                      clip_in=np.array(clip_in, np.float64), clip_out=np.array(clip_out, np.int64),
+                      bb_out=np.array(bb_out, np.int64), **{f"border{i}": borders[i] for i in range(8)}),
+                 {f"border{i}": borders[i] for i in range(8, 16)}, {f"border{i}": borders[i] for i in range(16, 24)})
     print("golden vectors written to", OUT)
 
 

@@ -6,7 +6,8 @@
 # Logs go to gpurun_out/<tag>/<n>_<kind>.log. Steps:
 #   suite [pytest -k expr]        the -m gpu suite (one process)
 #   smoke                         __graft_entry__.smoke()
-#   bench <workload> [args...]    bench.py --workload <workload> (c2 / c3 / c4 / c5)
+#   bench <workload> [args...]    bench.py --workload <workload> (c2 / c3 / c4 / c5); add --full for the
+#                                 CPU baseline, parity, HBM and breakdown blocks
 #   profile <tag>                 tools/profile_round.sh (kernel trace + PMC traffic + MFMA busy)
 #   pmc <match> <script> [args]   tools/pmc_cmd.sh counter passes over one python script
 #   probe <script> [args...]      python tools/<script> args
