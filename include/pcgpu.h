@@ -67,8 +67,9 @@ extern "C" {
  * exact f32 (parity runs against the CPU oracle). */
 #define PC_PREC_F16 0
 #define PC_PREC_F32 1
-/* pc_arcface_prep only: the centred chip x - 127.5 in f16 (exact), the input of the f16x3 IResNet
- * program (its stem weights carry the 1/127.5; models.compile_iresnet(split=True)) */
+/* pc_arcface_prep / pc_clip_prep only: the centred pixels x - 127.5 in f16 (exact), the input of the
+ * f16x3 IResNet program (its stem weights carry the 1/127.5; models.compile_iresnet(split=True)) and
+ * of the f16x3 ViT tower (doubled rows, see pc_clip_prep) */
 #define PC_PREC_F16X3 2
 
 typedef struct pc_ctx pc_ctx;
@@ -285,9 +286,17 @@ int pc_yolo_pose_detect(pc_net* net, const pc_yolo_letterbox_desc* h_descs, int 
                         float* d_dets, float* d_kpts, int32_t* d_count, int32_t* d_ncand);
 
 /* ---- ReID body embedding (OpenCLIP ViT-L/14 image tower) ---- */
-/* preprocess n crops -> ViT-L/14 patch matrix [n][257][608] (token 0 and K padding zero) */
+/* preprocess n crops -> ViT-L/14 patch matrix [n][257][608] (token 0 and K padding zero), normalised, in the
+ * precision's dtype. PC_PREC_F16X3: [n][257][1216] f16, each row the centred pixels x - 127.5 (x the
+ * Pillow-resampled u8 value; exact in f16) written twice as two 608-wide halves, token 0 and columns
+ * 588..607 of each half zero - the input of the f16x3 tower, whose program carries the normalisation
+ * (models_clip.compile_clip_vit(split=True)). */
 int pc_clip_prep(pc_ctx* ctx, int precision, const pc_crop_desc* h_crops, int n, void* d_out);
-/* preprocess + image tower + F.normalize: d_feat [n][dim] unit f32 */
+/* preprocess + image tower + F.normalize: d_feat [n][dim] unit f32. The net's input selects the
+ * preprocessing: 1x257x608 the normalised matrix in the net's dtype; 1x257x1216 flagged centred on an
+ * f16 net the PC_PREC_F16X3 form (any other width / flag combination: PC_ERR_FORMAT, nothing launched).
+ * The f16x3 tower holds its weights as [W_hi, W_hi, W_lo] f16 (6 bytes per parameter against 4 for
+ * f32) and its activations as [hi | lo] pairs (twice the f16 arena). */
 int pc_clip_embed(pc_net* net, const pc_crop_desc* h_crops, int n, float* d_feat);
 /* rows of d_e (stride ld floats) / max(||row||, eps) -> d_out [n][dim] */
 int pc_l2_normalize(pc_ctx* ctx, const float* d_e, int ld, int n, int dim, float eps, float* d_out);

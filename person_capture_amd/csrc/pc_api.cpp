@@ -109,10 +109,10 @@ struct UpsampleParams { const void* x; int N, H, W, C, xcs; void* y; int ycs; };
 hipError_t upsample2_launch(int f32, const UpsampleParams& p, hipStream_t s);
 struct LayerNormParams {
   const void* x; int xcs; void* y; int ycs; int M, C, cwrite;
-  const float* gamma; const float* beta; const float* add; int rows; float eps;
+  const float* gamma; const float* beta; const float* add; int rows; float eps; int xlo, ylo;
 };
 hipError_t layernorm_launch(int f32, const LayerNormParams& p, hipStream_t s);
-struct AttnParams { const void* qkv; int qcs; void* out; int ocs; int N, T, heads; float scale; };
+struct AttnParams { const void* qkv; int qcs; void* out; int ocs; int N, T, heads; float scale; int qlo, olo; };
 hipError_t attention_launch(int f32, const AttnParams& p, int head_dim, hipStream_t s);
 // pc_yolo.hip
 struct YoloLetterboxDesc;
@@ -136,7 +136,7 @@ struct ClipPrepDesc {
   const uint8_t* src; int H, W, row_stride; int kh, kv;
   const int* hb; const int* hk; const int* vb; const int* vk; int row0, nrows; uint8_t* tmp;
 };
-hipError_t clip_prep_launch(int f32, const ClipPrepDesc* d_descs, int N, int max_rows, void* out, hipStream_t s);
+hipError_t clip_prep_launch(int mode, const ClipPrepDesc* d_descs, int N, int max_rows, void* out, hipStream_t s);
 }  // namespace pc
 
 using namespace pc;
@@ -1378,8 +1378,8 @@ extern "C" int pc_net_create(pc_ctx* c, const void* prog, size_t nbytes, int pre
   }
   const float* data = (const float*)(P + pos);
   const size_t ndata = nw - pos;
-  // f16x3 split tensors: f16 nets only; only convs, the fused stem and the max
-  // pool read or write them
+  // f16x3 split tensors: f16 nets only; convs, the fused stem, the max pool,
+  // LayerNorm and attention (both tensors split) read or write them
   for (auto& t : n->tens)
     if (t.split && (n->f32 || t.is_f32 || t.buf < 0 || t.C % 16 || t.cs != t.C)) {
       delete n;
@@ -1403,12 +1403,23 @@ extern "C" int pc_net_create(pc_ctx* c, const void* prog, size_t nbytes, int pre
   for (auto& op : n->ops) {
     const int k = op.w[0];
     auto bad = [&](int t) { return t >= 0 && t < (int)n->tens.size() && n->tens[t].split; };
+    // LayerNorm / attention: both tensors split (pc_ops.hip SP forms) or neither
     if ((k == OP_MAXPOOL && (n->tens[op.w[1]].split != n->tens[op.w[2]].split ||
                              (n->tens[op.w[2]].split && n->tens[op.w[1]].C != n->tens[op.w[2]].C))) ||
-        ((k == OP_UPSAMPLE || k == OP_LAYERNORM || k == OP_ATTENTION) && (bad(op.w[1]) || bad(op.w[2]))) ||
+        (k == OP_UPSAMPLE && (bad(op.w[1]) || bad(op.w[2]))) ||
+        ((k == OP_LAYERNORM || k == OP_ATTENTION) && bad(op.w[1]) != bad(op.w[2])) ||
         (k == OP_STEM && bad(op.w[2]))) {
       delete n;
       return fail(c, PC_ERR_FORMAT, "op cannot read or write split tensors");
+    }
+    // split LayerNorm / attention: the logical width fits one half of either tensor
+    if ((k == OP_LAYERNORM || k == OP_ATTENTION) && bad(op.w[1])) {
+      const int cin = k == OP_LAYERNORM ? op.w[8] : 3 * op.w[3] * op.w[4];
+      const int cout = k == OP_LAYERNORM ? op.w[8] : op.w[3] * op.w[4];
+      if (cin <= 0 || cin > n->tens[op.w[2]].C / 2 || cout > n->tens[op.w[1]].C / 2) {
+        delete n;
+        return fail(c, PC_ERR_FORMAT, "split layernorm / attention wider than its tensors' halves");
+      }
     }
   }
   // which arrays are conv weights (uploaded in the activation dtype)
@@ -1838,6 +1849,8 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
       p.x = tensor_ptr(n, w[2]); p.xcs = X.cs;
       p.y = tensor_ptr(n, w[1]); p.ycs = Y.cs;
       p.M = N * X.H * X.W; p.C = w[8]; p.cwrite = Y.C;
+      p.xlo = p.ylo = 0;
+      if (X.split) { p.xlo = X.C / 2; p.ylo = p.cwrite = Y.C / 2; }   // (create checked Y.split == X.split)
       p.gamma = (const float*)n->arrays[w[3]];
       p.beta = (const float*)n->arrays[w[4]];
       p.add = w[5] >= 0 ? (const float*)n->arrays[w[5]] : nullptr;
@@ -1852,6 +1865,8 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
       p.out = tensor_ptr(n, w[1]); p.ocs = O.cs;
       p.N = N; p.T = Q.H * Q.W; p.heads = w[3];
       p.scale = 1.0f / sqrtf((float)w[4]);
+      p.qlo = Q.split ? Q.C / 2 : 0;
+      p.olo = O.split ? O.C / 2 : 0;
       HIPCHK(c, attention_launch(n->f32, p, w[4], s));
     }
     if (n->calib && (w[0] == OP_CONV || w[0] == OP_STEM)) {   // pc_net_calibrate: max |x| of the op's output
@@ -2503,7 +2518,8 @@ extern "C" int pc_clip_prep(pc_ctx* c, int prec, const pc_crop_desc* h, int n, v
   }
   void* ddesc;
   if ((rc = stage_copy(c, descs.data(), sizeof(ClipPrepDesc) * n, &ddesc))) return rc;
-  HIPCHK(c, clip_prep_launch(prec == PC_PREC_F32, (const ClipPrepDesc*)ddesc, n, max_rows, out, c->stream));
+  HIPCHK(c, clip_prep_launch(prec == PC_PREC_F32 ? 1 : (prec == PC_PREC_F16X3 ? 2 : 0), (const ClipPrepDesc*)ddesc, n,
+                             max_rows, out, c->stream));
   return PC_OK;
 }
 
@@ -2513,14 +2529,18 @@ extern "C" int pc_clip_embed(pc_net* net, const pc_crop_desc* h, int n, float* f
   if (n == 0) return PC_OK;
   if (n > net->max_batch) return fail(c, PC_ERR_ARG, "pc_clip_embed: batch exceeds max batch");
   const NetTensor& I = net->tens[net->in_tensor];
-  if (I.H != 1 || I.W != kClipTok || I.C != kClipK) return fail(c, PC_ERR_FORMAT, "CLIP net input must be 1x257x608");
-  const size_t need = (size_t)net->max_batch * kClipTok * kClipK * (net->f32 ? 4 : 2);
+  // the f16x3 tower (models_clip.compile_clip_vit(split=True)): a centred input of doubled rows on an f16 net
+  const bool x3 = I.C == 2 * kClipK;
+  if (I.H != 1 || I.W != kClipTok || (I.C != kClipK && !x3)) return fail(c, PC_ERR_FORMAT, "CLIP net input must be 1x257x608");
+  if (x3 ? (!net->in_centered || net->f32 || I.split) : net->in_centered)
+    return fail(c, PC_ERR_FORMAT, "CLIP net input: 1x257x1216 centred on an f16 net (f16x3 tower) or 1x257x608 normalised");
+  const size_t need = (size_t)net->max_batch * kClipTok * I.C * (net->f32 ? 4 : 2);
   if (net->prep_bytes < need) {
     if (net->prep) HIPCHK(c, hipFree(net->prep));
     HIPCHK(c, hipMalloc(&net->prep, need));
     net->prep_bytes = need;
   }
-  int rc = pc_clip_prep(c, net->f32 ? PC_PREC_F32 : PC_PREC_F16, h, n, net->prep);
+  int rc = pc_clip_prep(c, net->f32 ? PC_PREC_F32 : (x3 ? PC_PREC_F16X3 : PC_PREC_F16), h, n, net->prep);
   if (rc) return rc;
   rc = pc_net_run(net, net->prep, n);
   if (rc) return rc;

@@ -64,15 +64,22 @@ __global__ void clip_hpass(const ClipPrepDesc* __restrict__ descs) {
   o[2] = (uint8_t)clip8(s2);
 }
 
-// pass 2: vertical resample + ToTensor + Normalize, scattered into the patch matrix
-template <typename T>
+// pass 2: vertical resample + ToTensor + Normalize, scattered into the patch matrix.
+// CENTRED (f16x3 tower, T = f16): rows of 2 x 608, both halves the resampled u8 pixel minus 127.5
+// (exact in f16); the normalisation is folded into the program (models_clip.compile_clip_vit).
+template <typename T, bool CENTRED = false>
 __global__ void clip_vpass_patch(const ClipPrepDesc* __restrict__ descs, T* __restrict__ out) {
   const int n = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= CLIP_TOK * CLIP_KPAD) return;
   const int tok = i / CLIP_KPAD, kc = i - (i / CLIP_KPAD) * CLIP_KPAD;
-  T* o = out + (long long)n * CLIP_TOK * CLIP_KPAD + i;
-  if (tok == 0 || kc >= CLIP_K) { *o = (T)0.f; return; }
+  constexpr int ROW = CENTRED ? 2 * CLIP_KPAD : CLIP_KPAD;
+  T* o = out + ((long long)n * CLIP_TOK + tok) * ROW + kc;
+  if (tok == 0 || kc >= CLIP_K) {
+    *o = (T)0.f;
+    if constexpr (CENTRED) o[CLIP_KPAD] = (T)0.f;
+    return;
+  }
   const int pt = tok - 1, py = pt / CLIP_GRID, pxx = pt - (pt / CLIP_GRID) * CLIP_GRID;
   const int tap = kc / 3, c = kc - (kc / 3) * 3;   // c: RGB channel
   const int y = py * CLIP_PATCH + tap / CLIP_PATCH, x = pxx * CLIP_PATCH + tap % CLIP_PATCH;
@@ -82,17 +89,23 @@ __global__ void clip_vpass_patch(const ClipPrepDesc* __restrict__ descs, T* __re
   const int bc = 2 - c;   // BGR source channel
   int s = 1 << 21;
   for (int j = 0; j < yn; ++j) s += (int)d.tmp[((long long)(ymin + j) * CLIP_SIDE + x) * 3 + bc] * k[j];
+  if constexpr (CENTRED) {
+    o[0] = o[CLIP_KPAD] = (T)((float)clip8(s) - 127.5f);
+    return;
+  }
   const float v = (float)clip8(s) / 255.f;
   const float mean = c == 0 ? 0.48145466f : (c == 1 ? 0.4578275f : 0.40821073f);
   const float stdv = c == 0 ? 0.26862954f : (c == 1 ? 0.26130258f : 0.27577711f);
   *o = (T)((v - mean) / stdv);
 }
 
-hipError_t clip_prep_launch(int f32, const ClipPrepDesc* d_descs, int N, int max_rows, void* out, hipStream_t s) {
+// mode: 0 f16, 1 f32 (normalised [257][608]), 2 centred f16 [257][1216]
+hipError_t clip_prep_launch(int mode, const ClipPrepDesc* d_descs, int N, int max_rows, void* out, hipStream_t s) {
   dim3 g1((max_rows * CLIP_SIDE + 255) / 256, N);
   hipLaunchKernelGGL(clip_hpass, g1, dim3(256), 0, s, d_descs);
   dim3 g2((CLIP_TOK * CLIP_KPAD + 255) / 256, N);
-  if (f32) hipLaunchKernelGGL(clip_vpass_patch<float>, g2, dim3(256), 0, s, d_descs, (float*)out);
+  if (mode == 2) hipLaunchKernelGGL((clip_vpass_patch<f16, true>), g2, dim3(256), 0, s, d_descs, (f16*)out);
+  else if (mode == 1) hipLaunchKernelGGL(clip_vpass_patch<float>, g2, dim3(256), 0, s, d_descs, (float*)out);
   else hipLaunchKernelGGL(clip_vpass_patch<f16>, g2, dim3(256), 0, s, d_descs, (f16*)out);
   return hipGetLastError();
 }

@@ -64,6 +64,8 @@ struct LayerNormParams {
   const float* add;    // [rows][C] or null
   int rows;            // tokens per image (add table rows)
   float eps;
+  int xlo, ylo;        // f16x3 split rows (both or neither): the lo halves at +xlo / +ylo elements; C and
+                       // cwrite count one half (0: plain)
 };
 
 constexpr int LN_MAXV = 32;   // C <= 64 * 32 = 2048
@@ -80,7 +82,10 @@ __device__ __forceinline__ void ln_unpack(const f16x8& r, float* o) {
 // store per vector. The first version kept a 32-entry per-channel array with per-entry
 // bounds checks; the compiler hoisted 32 sets of addresses and spilled ~6200 VGPRs to
 // scratch (1.5 ms per ViT-L layernorm of 32 crops instead of ~15 us).
-template <typename T>
+//
+// SP (T = f16): f16x3 split rows. x = hi + lo per channel in f32, then the same arithmetic; the
+// output is written hi = f16(v), lo = f16(v - hi), one 16-byte store per half.
+template <typename T, bool SP = false>
 __global__ __launch_bounds__(256) void layernorm_vec(LayerNormParams p) {
   constexpr int V = 16 / sizeof(T);
   using VT = typename std::conditional<sizeof(T) == 4, f32x4, f16x8>::type;
@@ -99,6 +104,12 @@ __global__ __launch_bounds__(256) void layernorm_vec(LayerNormParams p) {
     for (int i = 0; i < V; ++i) v[k][i] = 0.f;
     if (vi < nv) {
       ln_unpack(*reinterpret_cast<const VT*>(xr + vi * V), v[k]);
+      if constexpr (SP) {
+        float l[V];
+        ln_unpack(*reinterpret_cast<const VT*>(xr + p.xlo + vi * V), l);
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[k][i] += l[i];
+      }
       if (ar) {
 #pragma unroll
         for (int i = 0; i < V; i += 4) {
@@ -129,57 +140,81 @@ __global__ __launch_bounds__(256) void layernorm_vec(LayerNormParams p) {
   for (int k = 0; k < LN_NIT; ++k) {
     const int vi = lane + 64 * k;
     if (vi < nv) {
-      VT o;
+      VT o, ol;
 #pragma unroll
       for (int i = 0; i < V; i += 4) {
         const f32x4 g = *reinterpret_cast<const f32x4*>(p.gamma + vi * V + i);
         const f32x4 b = *reinterpret_cast<const f32x4*>(p.beta + vi * V + i);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[i + j] = (T)((v[k][i + j] - mean) * rstd * g[j] + b[j]);
+        for (int j = 0; j < 4; ++j) {
+          const float r = (v[k][i + j] - mean) * rstd * g[j] + b[j];
+          o[i + j] = (T)r;
+          if constexpr (SP) ol[i + j] = (T)(r - (float)o[i + j]);
+        }
       }
       *reinterpret_cast<VT*>(yr + vi * V) = o;
+      if constexpr (SP) *reinterpret_cast<VT*>(yr + p.ylo + vi * V) = ol;
     }
   }
-  for (int c = p.C + lane; c < p.cwrite; c += 64) yr[c] = (T)0.f;
+  for (int c = p.C + lane; c < p.cwrite; c += 64) {
+    yr[c] = (T)0.f;
+    if constexpr (SP) yr[p.ylo + c] = (T)0.f;
+  }
 }
 
 // Any shape (rows not 16-byte aligned): two passes over the row from memory (L2), no
 // per-lane arrays.
-template <typename T>
+template <typename T, bool SP = false>
 __global__ __launch_bounds__(256) void layernorm_rows(LayerNormParams p) {
   const int lane = threadIdx.x & 63;
   const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (tok >= p.M) return;
   const T* xr = reinterpret_cast<const T*>(p.x) + (size_t)tok * p.xcs;
   const float* ar = p.add ? p.add + (size_t)(tok % p.rows) * p.C : nullptr;
+  // the row's value: a split row (SP) is hi + lo
+  auto xv = [&](int c) {
+    float v = (float)xr[c];
+    if constexpr (SP) v += (float)xr[p.xlo + c];
+    return v + (ar ? ar[c] : 0.f);
+  };
   float s = 0.f;
-  for (int c = lane; c < p.C; c += 64) s += (float)xr[c] + (ar ? ar[c] : 0.f);
+  for (int c = lane; c < p.C; c += 64) s += xv(c);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   const float mean = s / (float)p.C;
   float q = 0.f;
   for (int c = lane; c < p.C; c += 64) {
-    const float d = (float)xr[c] + (ar ? ar[c] : 0.f) - mean;
+    const float d = xv(c) - mean;
     q += d * d;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
   const float rstd = 1.0f / sqrtf(q / (float)p.C + p.eps);
   T* yr = reinterpret_cast<T*>(p.y) + (size_t)tok * p.ycs;
-  for (int c = lane; c < p.cwrite; c += 64)
-    yr[c] = c < p.C ? (T)(((float)xr[c] + (ar ? ar[c] : 0.f) - mean) * rstd * p.gamma[c] + p.beta[c]) : (T)0.f;
+  for (int c = lane; c < p.cwrite; c += 64) {
+    const float r = c < p.C ? (xv(c) - mean) * rstd * p.gamma[c] + p.beta[c] : 0.f;
+    const T hi = (T)r;
+    yr[c] = hi;
+    if constexpr (SP) yr[p.ylo + c] = (T)(r - (float)hi);   // f16x3 output: lo = f16(v - f16(v))
+  }
 }
 
 hipError_t layernorm_launch(int f32, const LayerNormParams& p, hipStream_t s) {
   if (p.C > 64 * LN_MAXV || p.cwrite > 64 * LN_MAXV || p.M <= 0) return hipErrorInvalidValue;
+  const bool sp = p.xlo != 0;
+  if (sp != (p.ylo != 0) || (sp && (f32 || p.xlo < p.C || p.ylo < p.cwrite || p.xlo + p.C > p.xcs || p.ylo + p.cwrite > p.ycs)))
+    return hipErrorInvalidValue;
   dim3 grid((unsigned)((p.M + 3) / 4));
   const int V = f32 ? 4 : 8;
   // the in-place case (y == x) is safe for both kernels: a wave reads its whole row before writing it
   const bool vec = p.C % V == 0 && p.xcs % V == 0 && p.ycs % V == 0 && p.C / V <= 64 * LN_NIT &&
                    (reinterpret_cast<uintptr_t>(p.x) % 16) == 0 && (reinterpret_cast<uintptr_t>(p.y) % 16) == 0 &&
                    (reinterpret_cast<uintptr_t>(p.gamma) % 16) == 0 && (reinterpret_cast<uintptr_t>(p.beta) % 16) == 0 &&
-                   (!p.add || (reinterpret_cast<uintptr_t>(p.add) % 16) == 0);
-  if (vec) {
+                   (!p.add || (reinterpret_cast<uintptr_t>(p.add) % 16) == 0) && p.xlo % V == 0 && p.ylo % V == 0;
+  if (sp) {
+    if (vec) hipLaunchKernelGGL((layernorm_vec<f16, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((layernorm_rows<f16, true>), grid, dim3(256), 0, s, p);
+  } else if (vec) {
     if (f32) hipLaunchKernelGGL(layernorm_vec<float>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(layernorm_vec<f16>, grid, dim3(256), 0, s, p);
   } else {
@@ -195,6 +230,7 @@ struct AttnParams {
   void* out; int ocs;         // [N][T][ocs]
   int N, T, heads;
   float scale;                // 1/sqrt(head_dim)
+  int qlo, olo;               // f16x3 split rows (both or neither): the lo halves at +qlo / +olo elements (0: plain)
 };
 
 constexpr int ATT_D = 64;         // head dim
@@ -203,8 +239,12 @@ constexpr int ATT_WAVES = 4;      // waves split the keys
 constexpr int ATT_TMAX = 272;     // max tokens staged in LDS (257 for ViT-L/14 @ 224)
 constexpr int ATT_CHUNK = 16;     // keys scored per online-softmax update
 
-template <typename T>
+// SP (T = float): f16x3 split rows of an f16 net. q, k and v are read as hi + lo in f32 (K and V
+// staged as the f32 sums: the <float> kernel's LDS), scores, softmax and combine are the f32
+// kernel's, and the output is written hi = f16(v), lo = f16(v - hi).
+template <typename T, bool SP = false>
 __global__ __launch_bounds__(256) void mha_tokens(AttnParams p) {
+  using S = typename std::conditional<SP, f16, T>::type;   // storage type of qkv / out
   constexpr int KV_BYTES = 2 * ATT_TMAX * ATT_D * (int)sizeof(T);
   constexpr int CMB_BYTES = ATT_WAVES * ATT_Q * (ATT_D + 2) * 4;
   constexpr int SMEM = KV_BYTES > CMB_BYTES ? KV_BYTES : CMB_BYTES;
@@ -216,23 +256,39 @@ __global__ __launch_bounds__(256) void mha_tokens(AttnParams p) {
   const int h = (blockIdx.x / nqb) % p.heads;
   const int n = blockIdx.x / (nqb * p.heads);
   const int E = p.heads * ATT_D;
-  const T* base = reinterpret_cast<const T*>(p.qkv) + (long long)n * p.T * p.qcs;
+  const S* base = reinterpret_cast<const S*>(p.qkv) + (long long)n * p.T * p.qcs;
   // stage K and V of this head (16-byte vectors)
-  constexpr int VE = 16 / sizeof(T);
+  constexpr int VE = 16 / sizeof(S);
   for (int i = threadIdx.x; i < p.T * (ATT_D / VE); i += blockDim.x) {
     const int t = i / (ATT_D / VE), c = (i % (ATT_D / VE)) * VE;
-    const T* row = base + (long long)t * p.qcs + h * ATT_D + c;
-    *reinterpret_cast<f32x4*>(Ks + t * ATT_D + c) = *reinterpret_cast<const f32x4*>(row + E);
-    *reinterpret_cast<f32x4*>(Vs + t * ATT_D + c) = *reinterpret_cast<const f32x4*>(row + 2 * E);
+    const S* row = base + (long long)t * p.qcs + h * ATT_D + c;
+    if constexpr (SP) {
+      const f16x8 kh = *reinterpret_cast<const f16x8*>(row + E), kl = *reinterpret_cast<const f16x8*>(row + E + p.qlo);
+      const f16x8 vh = *reinterpret_cast<const f16x8*>(row + 2 * E), vl = *reinterpret_cast<const f16x8*>(row + 2 * E + p.qlo);
+#pragma unroll
+      for (int j = 0; j < 8; j += 4) {
+        f32x4 kf, vf;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { kf[u] = (float)kh[j + u] + (float)kl[j + u]; vf[u] = (float)vh[j + u] + (float)vl[j + u]; }
+        *reinterpret_cast<f32x4*>(Ks + t * ATT_D + c + j) = kf;
+        *reinterpret_cast<f32x4*>(Vs + t * ATT_D + c + j) = vf;
+      }
+    } else {
+      *reinterpret_cast<f32x4*>(Ks + t * ATT_D + c) = *reinterpret_cast<const f32x4*>(row + E);
+      *reinterpret_cast<f32x4*>(Vs + t * ATT_D + c) = *reinterpret_cast<const f32x4*>(row + 2 * E);
+    }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int qi = qb * ATT_Q + lane;
   const bool qok = qi < p.T;
   float q[ATT_D];
   {
-    const T* qr = base + (long long)(qok ? qi : 0) * p.qcs + h * ATT_D;
+    const S* qr = base + (long long)(qok ? qi : 0) * p.qcs + h * ATT_D;
 #pragma unroll
-    for (int c = 0; c < ATT_D; ++c) q[c] = (float)qr[c] * p.scale;
+    for (int c = 0; c < ATT_D; ++c) {
+      if constexpr (SP) q[c] = ((float)qr[c] + (float)qr[p.qlo + c]) * p.scale;
+      else q[c] = (float)qr[c] * p.scale;
+    }
   }
   __syncthreads();
   // this wave's key range
@@ -301,15 +357,30 @@ __global__ __launch_bounds__(256) void mha_tokens(AttnParams p) {
     L += cmb[(w * ATT_Q + lane) * (ATT_D + 2) + 1] * f[w];
   }
   const float inv = 1.0f / L;
-  T* orow = reinterpret_cast<T*>(p.out) + ((long long)n * p.T + qi) * p.ocs + h * ATT_D;
+  S* orow = reinterpret_cast<S*>(p.out) + ((long long)n * p.T + qi) * p.ocs + h * ATT_D;
   constexpr int DW = ATT_D / ATT_WAVES;
+  f16x8 oh[DW / 8], ol[DW / 8];
 #pragma unroll
   for (int c = 0; c < DW; ++c) {
     const int d = wave * DW + c;
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < ATT_WAVES; ++w) v += cmb[(w * ATT_Q + lane) * (ATT_D + 2) + 2 + d] * f[w];
-    orow[d] = (T)(v * inv);
+    if constexpr (SP) {
+      const float r = v * inv;
+      const f16 hi = (f16)r;
+      oh[c / 8][c % 8] = hi;
+      ol[c / 8][c % 8] = (f16)(r - (float)hi);
+    } else {
+      orow[d] = (T)(v * inv);
+    }
+  }
+  if constexpr (SP) {
+#pragma unroll
+    for (int g = 0; g < DW / 8; ++g) {
+      *reinterpret_cast<f16x8*>(orow + wave * DW + g * 8) = oh[g];
+      *reinterpret_cast<f16x8*>(orow + p.olo + wave * DW + g * 8) = ol[g];
+    }
   }
 }
 
@@ -317,7 +388,13 @@ hipError_t attention_launch(int f32, const AttnParams& p, int head_dim, hipStrea
   if (head_dim != ATT_D || p.T > ATT_TMAX || p.T <= 0 || p.qcs % 8 || p.heads <= 0) return hipErrorInvalidValue;
   const int nqb = (p.T + ATT_Q - 1) / ATT_Q;
   dim3 grid((unsigned)(p.N * p.heads * nqb));
-  if (f32) hipLaunchKernelGGL(mha_tokens<float>, grid, dim3(64 * ATT_WAVES), 0, s, p);
+  const bool sp = p.qlo != 0;
+  const int E = p.heads * ATT_D;
+  if (sp != (p.olo != 0) || (sp && (f32 || p.qlo % 8 || p.olo % 8 || p.ocs % 8 || p.qlo < 3 * E || p.qlo + 3 * E > p.qcs ||
+                                    p.olo < E || p.olo + E > p.ocs)))
+    return hipErrorInvalidValue;
+  if (sp) hipLaunchKernelGGL((mha_tokens<float, true>), grid, dim3(64 * ATT_WAVES), 0, s, p);
+  else if (f32) hipLaunchKernelGGL(mha_tokens<float>, grid, dim3(64 * ATT_WAVES), 0, s, p);
   else hipLaunchKernelGGL(mha_tokens<f16>, grid, dim3(64 * ATT_WAVES), 0, s, p);
   return hipGetLastError();
 }

@@ -18,6 +18,7 @@ the patch matrix the preprocessing kernel writes ([257][608]: 14*14*3 = 588 colu
 padded to 608, token 0 zero), the class/positional embedding is the additive table of
 the ln_pre LayerNorm op, attention is OP_ATTENTION, and the final projection is a 1x1
 conv with stride 257 that reads only the class token of every image.
+compile_clip_vit(split=True) builds the f16x3 form of the same program.
 """
 from __future__ import annotations
 
@@ -38,6 +39,9 @@ CLIP_CFGS = {
     "ViT-tiny-14": dict(width=128, layers=2, heads=2, mlp=512, out=64, patch=14, image=224),
 }
 LN_EPS = 1e-5
+# open_clip OPENAI_DATASET_MEAN / OPENAI_DATASET_STD (RGB), as pc_clip.hip normalises
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 def clip_cfg(name: str) -> dict:
@@ -98,22 +102,43 @@ def _lin(P: Program, out: int, x: int, W: np.ndarray, b, act: int = ACT_NONE, re
            res_mode=RES_SAME, act_after_res=0)
 
 
-def compile_clip_vit(p: Params, name: str = "ViT-L-14") -> Program:
+def compile_clip_vit(p: Params, name: str = "ViT-L-14", split: bool = False) -> Program:
     """Image tower -> program. Input: patch matrix [1][T][608] (see module doc). Output:
-    f32 [1][1][out_dim] per image (before F.normalize)."""
+    f32 [1][1][out_dim] per image (before F.normalize).
+
+    split=True: the f16x3 form for an f16 net. Every f16 activation is a
+    [hi | lo] pair. The input stays a plain f16 tensor [1][T][2*608] that holds the centred u8
+    patch matrix x - 127.5 twice (exact in f16; token 0 and the K padding zero), and the patch
+    embedding is a plain 1x1 conv over K = 1216 against [W'_hi | W'_lo], W' = W / (255 std_c):
+    x W'_hi + x W'_lo, so conv1 is never rounded to f16. The normalisation mean goes into the
+    ln_pre add table (not a conv bias), so token 0 stays the class token."""
     c = clip_cfg(name)
     w, L, heads, od = c["width"], c["layers"], c["heads"], c["out"]
     g = c["image"] // c["patch"]
     T = g * g + 1
     K = 3 * c["patch"] ** 2
-    P = Program()
-    x_in = P.input_tensor(1, T, cpad(K))
+    kp = cpad(K)
+    P = Program(split=split)
+    x_in = P.input_tensor(1, T, 2 * kp if split else kp)
     # patch embedding: conv1 weight [w][3][14][14] -> [w][(kh*14 + kw)*3 + c]
     Wc = np.transpose(p["visual.conv1.weight"], (0, 2, 3, 1)).reshape(w, K)
     e = P.act(1, T, w)
-    _lin(P, e, x_in, Wc, None)
-    x = P.act(1, T, w)
     add = p["visual.positional_embedding"].astype(np.float64).copy()
+    if split:
+        P.input_centered = True
+        mean = np.tile(np.array(CLIP_MEAN, np.float64), K // 3)
+        std = np.tile(np.array(CLIP_STD, np.float64), K // 3)
+        Ws = Wc.astype(np.float64) / (255.0 * std)
+        hi = Ws.astype(np.float16).astype(np.float64)
+        Wp = np.zeros((w, 2 * kp), np.float32)
+        Wp[:, :K] = hi
+        Wp[:, kp:kp + K] = (Ws - hi).astype(np.float16)
+        _lin(P, e, x_in, Wp, None)
+        # (x/255 - mean)/std = (x - 127.5)/(255 std) - (mean - 0.5)/std
+        add[1:] -= (Wc.astype(np.float64) * ((mean - 0.5) / std)).sum(1)
+    else:
+        _lin(P, e, x_in, Wc, None)
+    x = P.act(1, T, w)
     add[0] += p["visual.class_embedding"]
     P.layernorm(x, e, p["visual.ln_pre.weight"], p["visual.ln_pre.bias"], LN_EPS, add=add)
     for i in range(L):

@@ -25,7 +25,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import models_clip
-from ._lib import PC_PREC_F16, PC_PREC_F32, CropDesc, check
+from ._lib import PC_PREC_F16, PC_PREC_F16X3, PC_PREC_F32, CropDesc, check, net_precision
 from .runtime import GpuContext, Net
 
 _WEIGHTS: Dict[Tuple[str, int], dict] = {}
@@ -34,9 +34,12 @@ _WEIGHTS: Dict[Tuple[str, int], dict] = {}
 def _precision() -> int:
     """f32 by default: the reference runs encode_image in fp32 (reid_embedder.py:53-55) and
     no TensorRT engine exists for it. PERSON_CAPTURE_AMD_REID_PRECISION=f16 opts into the
-    f16 tower (narrower than the reference: tests/test_gpu_reid.py bounds it)."""
-    v = os.getenv("PERSON_CAPTURE_AMD_REID_PRECISION", "f32")
-    return PC_PREC_F16 if v.strip().lower() in ("f16", "fp16", "float16", "half") else PC_PREC_F32
+    f16 tower (narrower than the reference: tests/test_gpu_reid.py bounds it), =f16x3 into the
+    split tower (f32 class on the f16 matrix cores). Any other word runs f32."""
+    v = os.getenv("PERSON_CAPTURE_AMD_REID_PRECISION", "f32").strip().lower()
+    if v in ("f16x3", "x3", "split"):
+        return PC_PREC_F16X3
+    return PC_PREC_F16 if v in ("f16", "fp16", "float16", "half") else PC_PREC_F32
 
 
 def clip_weights(name: str, seed: int = 0) -> dict:
@@ -51,8 +54,10 @@ class ClipEngine:
 
     def __init__(self, ctx: GpuContext, params: dict, name: str, precision: int = PC_PREC_F16, max_batch: int = 32):
         self.ctx, self.name, self.max_batch = ctx, name, max_batch
-        self.program = models_clip.compile_clip_vit(params, name)
-        self.net = Net(ctx, self.program.serialize(), precision=precision, max_batch=max_batch)
+        self.precision = precision
+        # PC_PREC_F16X3: the split program on an f16 net (f32-class embeddings on f16 MFMA)
+        self.program = models_clip.compile_clip_vit(params, name, split=precision == PC_PREC_F16X3)
+        self.net = Net(ctx, self.program.serialize(), precision=net_precision(precision), max_batch=max_batch)
         self.dim = models_clip.clip_cfg(name)["out"]
 
     @property
@@ -75,6 +80,11 @@ class ReIDEmbedder:
     """
     Body embedding via an OpenCLIP ViT image tower on the MI355X.
     Defaults to ViT-L-14; returns L2-normalized embeddings as np.float32.
+
+    PERSON_CAPTURE_AMD_REID_PRECISION picks the tower's arithmetic: f32 (default, as the
+    reference), f16 (throughput, cosine >= 0.99 only) or f16x3 (f32 class on the f16 matrix
+    cores: unit embeddings within 1e-4 of the oracle; weights take 6 bytes per parameter against
+    4 for f32, activations twice the f16 arena).
     """
 
     def __init__(self, device: str = 'cuda', model_name: str = 'ViT-L-14', pretrained: str = 'laion2b_s32b_b82k',
