@@ -40,6 +40,9 @@
  *                                      res.boxes + res.keypoints.xy (face_embedder.py:1680-1703, 1391-1429)
  *   pc_clip_prep / pc_clip_embed       ReIDEmbedder.extract: BGR2RGB + open_clip preprocess + encode_image +
  *                                      F.normalize (reid_embedder.py:38-57)
+ *   pc_clip_prep_geom / pc_clip_embed_geom   the same for the other towers of ReIDEmbedder(model_name=...)
+ *                                      (reid_embedder.py:19-31; the GUI's reid_backbone, gui_app.py:429, 4511):
+ *                                      open_clip image_transform(image_size) + the tower's patch size
  *   pc_l2_normalize                    torch.nn.functional.normalize(feats, dim=1) (reid_embedder.py:55)
  *   pc_pil_bicubic_coeffs              Pillow Image.resize(BICUBIC) coefficients inside the open_clip
  *                                      preprocess (reid_embedder.py:49)
@@ -298,6 +301,17 @@ int pc_clip_prep(pc_ctx* ctx, int precision, const pc_crop_desc* h_crops, int n,
  * The f16x3 tower holds its weights as [W_hi, W_hi, W_lo] f16 (6 bytes per parameter against 4 for
  * f32) and its activations as [hi | lo] pairs (twice the f16 arena). */
 int pc_clip_embed(pc_net* net, const pc_crop_desc* h_crops, int n, float* d_feat);
+/* pc_clip_prep for any tower of the OpenCLIP ViT family (ReIDEmbedder(model_name=...),
+ * reid_embedder.py:19-31: open_clip preprocess at the model's image size): Resize(side) + CenterCrop(side)
+ * with side in {224, 336}, patches of `patch` in {14, 16, 32} pixels (side % patch == 0; else PC_ERR_ARG).
+ * d_out [n][T][Kp], T = (side / patch)^2 + 1, Kp = 3 patch^2 rounded up to 32 (PC_PREC_F16X3: [n][T][2 Kp]);
+ * same arithmetic and modes. pc_clip_prep is this call at (224, 14). */
+int pc_clip_prep_geom(pc_ctx* ctx, int precision, int side, int patch, const pc_crop_desc* h_crops, int n, void* d_out);
+/* pc_clip_embed for a tower of that geometry (ReIDEmbedder.extract, reid_embedder.py:38-57, with the
+ * model_name of reid_embedder.py:19-31). The net's input must be 1 x T x Kp (or 1 x T x 2 Kp flagged centred
+ * on an f16 net) for exactly this side and patch: anything else is PC_ERR_FORMAT before any launch - the
+ * geometry is never guessed from the padded width. pc_clip_embed is this call at (224, 14). */
+int pc_clip_embed_geom(pc_net* net, int side, int patch, const pc_crop_desc* h_crops, int n, float* d_feat);
 /* rows of d_e (stride ld floats) / max(||row||, eps) -> d_out [n][dim] */
 int pc_l2_normalize(pc_ctx* ctx, const float* d_e, int ld, int n, int dim, float eps, float* d_out);
 /* Pillow BICUBIC resample coefficients (precompute_coeffs + normalize_coeffs_8bpc) for output

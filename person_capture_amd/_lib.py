@@ -143,6 +143,8 @@ SIGNATURES = {
                              _I, _P, _P, _P, _P], _I),
     "pc_clip_prep": ([_P, _I, C.POINTER(CropDesc), _I, _P], _I),
     "pc_clip_embed": ([_P, C.POINTER(CropDesc), _I, _P], _I),
+    "pc_clip_prep_geom": ([_P, _I, _I, _I, C.POINTER(CropDesc), _I, _P], _I),
+    "pc_clip_embed_geom": ([_P, _I, _I, C.POINTER(CropDesc), _I, _P], _I),
     "pc_l2_normalize": ([_P, _P, _I, _I, _I, _F, _P], _I),
     "pc_pil_bicubic_coeffs": ([_I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I], _I),
     "pc_clip_geometry": ([_I, _I, _I, C.POINTER(C.c_int32)], _I),

@@ -113,7 +113,8 @@ struct LayerNormParams {
 };
 hipError_t layernorm_launch(int f32, const LayerNormParams& p, hipStream_t s);
 struct AttnParams { const void* qkv; int qcs; void* out; int ocs; int N, T, heads; float scale; int qlo, olo; };
-hipError_t attention_launch(int f32, const AttnParams& p, int head_dim, hipStream_t s);
+hipError_t attention_launch(int f32, const AttnParams& p, int head_dim, int stream_form, hipStream_t s);
+bool attention_head_dim_ok(int head_dim);
 // pc_yolo.hip
 struct YoloLetterboxDesc;
 hipError_t yolo_letterbox_launch(int f32, const YoloLetterboxDesc* d_descs, int N, int Hp, int Wp, void* out,
@@ -136,7 +137,8 @@ struct ClipPrepDesc {
   const uint8_t* src; int H, W, row_stride; int kh, kv;
   const int* hb; const int* hk; const int* vb; const int* vk; int row0, nrows; uint8_t* tmp;
 };
-hipError_t clip_prep_launch(int mode, const ClipPrepDesc* d_descs, int N, int max_rows, void* out, hipStream_t s);
+hipError_t clip_prep_launch(int mode, const ClipPrepDesc* d_descs, int N, int max_rows, int side, int patch, void* out,
+                            hipStream_t s);
 }  // namespace pc
 
 using namespace pc;
@@ -615,6 +617,7 @@ struct pc_net {
   std::vector<ChainPlan> chains;
   std::vector<int> chain_at;      // op index -> chain id (first op of a chain) or -1
   int chain_min_batch = 32;       // PC_CHAIN_MIN overrides (tuning)
+  int attn_stream = 0;            // PERSON_CAPTURE_AMD_ATTN=stream at create: pc_attn.hip for every attention shape
   std::vector<const float*> host_arrays;   // program arrays, valid during pc_net_create only
   void* stem_col = nullptr;   // im2col scratch shared by the stems
   float* partial = nullptr;
@@ -1392,6 +1395,14 @@ extern "C" int pc_net_create(pc_ctx* c, const void* prog, size_t nbytes, int pre
       delete n;
       return fail(c, PC_ERR_FORMAT, "f16c8 tensor: split storage of 32-channel blocks");
     }
+  // attention: a head dim one of the kernels covers (pc_ops.hip mha_tokens, pc_attn.hip), and the
+  // dispatch switch, read here once and kept for every launch of this net
+  for (auto& op : n->ops)
+    if (op.w[0] == OP_ATTENTION && (op.w[3] <= 0 || !attention_head_dim_ok(op.w[4]))) {
+      delete n;
+      return fail(c, PC_ERR_FORMAT, "attention: head dims 64 and 80 are implemented");
+    }
+  if (const char* e = getenv("PERSON_CAPTURE_AMD_ATTN")) n->attn_stream = strcmp(e, "stream") == 0;
   for (auto& op : n->ops) {
     const int k = op.w[0];
     auto c8t = [&](int t) { return t >= 0 && t < (int)n->tens.size() && n->tens[t].c8; };
@@ -1867,7 +1878,7 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
       p.scale = 1.0f / sqrtf((float)w[4]);
       p.qlo = Q.split ? Q.C / 2 : 0;
       p.olo = O.split ? O.C / 2 : 0;
-      HIPCHK(c, attention_launch(n->f32, p, w[4], s));
+      HIPCHK(c, attention_launch(n->f32, p, w[4], n->attn_stream, s));
     }
     if (n->calib && (w[0] == OP_CONV || w[0] == OP_STEM)) {   // pc_net_calibrate: max |x| of the op's output
       const NetTensor& Y = n->tens[w[1]];
@@ -2456,13 +2467,19 @@ extern "C" int pc_yolo_pose_detect(pc_net* net, const pc_yolo_letterbox_desc* h,
 }
 
 // ===========================================================================
-// ReID: OpenCLIP ViT-L/14 image tower (ReIDEmbedder.extract, reid_embedder.py:38-57)
+// ReID: OpenCLIP ViT image tower (ReIDEmbedder.extract, reid_embedder.py:38-57)
 // ===========================================================================
-static const int kClipSide = 224, kClipTok = 257, kClipK = 608, kClipKmax = 64;
+static const int kClipKmax = 64;
 
-extern "C" int pc_clip_prep(pc_ctx* c, int prec, const pc_crop_desc* h, int n, void* out) {
+// the tower geometries pc_clip.hip, the conv K tile and the attention kernels are tested at
+static bool clip_geom_ok(int side, int patch) {
+  return (side == 224 || side == 336) && (patch == 14 || patch == 16 || patch == 32) && side % patch == 0;
+}
+
+extern "C" int pc_clip_prep_geom(pc_ctx* c, int prec, int side, int patch, const pc_crop_desc* h, int n, void* out) {
   if (!c || !h || n <= 0 || !out) return fail(c, PC_ERR_ARG, "pc_clip_prep: bad arguments");
-  // host: geometry + Pillow coefficient tables for the 224 kept columns / rows of each crop
+  if (!clip_geom_ok(side, patch)) return fail(c, PC_ERR_ARG, "pc_clip_prep: side in {224, 336}, patch in {14, 16, 32}, side % patch == 0");
+  // host: geometry + Pillow coefficient tables for the `side` kept columns / rows of each crop
   struct Tabs { int kh, kv, row0, nrows; std::vector<int32_t> hb, hk, vb, vk; };
   std::vector<Tabs> T(n);
   size_t tmp_bytes = 0, tab_ints = 0;
@@ -2471,20 +2488,20 @@ extern "C" int pc_clip_prep(pc_ctx* c, int prec, const pc_crop_desc* h, int n, v
     const pc_crop_desc& d = h[i];
     if (!d.d_src || d.H <= 0 || d.W <= 0 || d.row_stride < d.W * 3) return fail(c, PC_ERR_ARG, "pc_clip_prep: bad crop");
     int32_t g[4];
-    pc_clip_geometry(d.H, d.W, kClipSide, g);
+    pc_clip_geometry(d.H, d.W, side, g);
     Tabs& t = T[i];
-    t.hb.resize(2 * kClipSide); t.vb.resize(2 * kClipSide);
-    t.hk.resize((size_t)kClipSide * kClipKmax); t.vk.resize((size_t)kClipSide * kClipKmax);
-    t.kh = pc_pil_bicubic_coeffs(d.W, g[0], g[3], kClipSide, t.hb.data(), t.hk.data(), kClipKmax);
-    t.kv = pc_pil_bicubic_coeffs(d.H, g[1], g[2], kClipSide, t.vb.data(), t.vk.data(), kClipKmax);
+    t.hb.resize(2 * side); t.vb.resize(2 * side);
+    t.hk.resize((size_t)side * kClipKmax); t.vk.resize((size_t)side * kClipKmax);
+    t.kh = pc_pil_bicubic_coeffs(d.W, g[0], g[3], side, t.hb.data(), t.hk.data(), kClipKmax);
+    t.kv = pc_pil_bicubic_coeffs(d.H, g[1], g[2], side, t.vb.data(), t.vk.data(), kClipKmax);
     if (t.kh < 0 || t.kv < 0) return fail(c, PC_ERR_CAPACITY, "pc_clip_prep: crop too large for the resample tables");
-    t.hk.resize((size_t)kClipSide * t.kh); t.vk.resize((size_t)kClipSide * t.kv);
+    t.hk.resize((size_t)side * t.kh); t.vk.resize((size_t)side * t.kv);
     int lo = 1 << 30, hi = 0;
-    for (int y = 0; y < kClipSide; ++y) { lo = std::min(lo, t.vb[2 * y]); hi = std::max(hi, t.vb[2 * y] + t.vb[2 * y + 1]); }
+    for (int y = 0; y < side; ++y) { lo = std::min(lo, t.vb[2 * y]); hi = std::max(hi, t.vb[2 * y] + t.vb[2 * y + 1]); }
     t.row0 = lo; t.nrows = std::max(hi - lo, 1);
-    for (int y = 0; y < kClipSide; ++y) t.vb[2 * y] -= lo;
+    for (int y = 0; y < side; ++y) t.vb[2 * y] -= lo;
     max_rows = std::max(max_rows, t.nrows);
-    tmp_bytes += (size_t)t.nrows * kClipSide * 3;
+    tmp_bytes += (size_t)t.nrows * side * 3;
     tab_ints += t.hb.size() + t.hk.size() + t.vb.size() + t.vk.size();
   }
   if (c->clip_tmp_bytes < tmp_bytes) {
@@ -2514,33 +2531,41 @@ extern "C" int pc_clip_prep(pc_ctx* c, int prec, const pc_crop_desc* h, int n, v
     d.hb = tb + off[4 * i]; d.hk = tb + off[4 * i + 1]; d.vb = tb + off[4 * i + 2]; d.vk = tb + off[4 * i + 3];
     d.row0 = T[i].row0; d.nrows = T[i].nrows;
     d.tmp = (uint8_t*)c->clip_tmp + tmp_off;
-    tmp_off += (size_t)T[i].nrows * kClipSide * 3;
+    tmp_off += (size_t)T[i].nrows * side * 3;
   }
   void* ddesc;
   if ((rc = stage_copy(c, descs.data(), sizeof(ClipPrepDesc) * n, &ddesc))) return rc;
   HIPCHK(c, clip_prep_launch(prec == PC_PREC_F32 ? 1 : (prec == PC_PREC_F16X3 ? 2 : 0), (const ClipPrepDesc*)ddesc, n,
-                             max_rows, out, c->stream));
+                             max_rows, side, patch, out, c->stream));
   return PC_OK;
 }
 
-extern "C" int pc_clip_embed(pc_net* net, const pc_crop_desc* h, int n, float* feat) {
+extern "C" int pc_clip_prep(pc_ctx* c, int prec, const pc_crop_desc* h, int n, void* out) {
+  return pc_clip_prep_geom(c, prec, 224, 14, h, n, out);
+}
+
+extern "C" int pc_clip_embed_geom(pc_net* net, int side, int patch, const pc_crop_desc* h, int n, float* feat) {
   if (!net || !h || n < 0 || !feat) return PC_ERR_ARG;
   pc_ctx* c = net->ctx;
+  if (!clip_geom_ok(side, patch)) return fail(c, PC_ERR_ARG, "pc_clip_embed: side in {224, 336}, patch in {14, 16, 32}, side % patch == 0");
   if (n == 0) return PC_OK;
   if (n > net->max_batch) return fail(c, PC_ERR_ARG, "pc_clip_embed: batch exceeds max batch");
   const NetTensor& I = net->tens[net->in_tensor];
+  // the net's input against the explicit geometry: [1][(side/patch)^2 + 1][cpad(3 patch^2)]
+  const int tok = (side / patch) * (side / patch) + 1, kpad = (3 * patch * patch + 31) / 32 * 32;
   // the f16x3 tower (models_clip.compile_clip_vit(split=True)): a centred input of doubled rows on an f16 net
-  const bool x3 = I.C == 2 * kClipK;
-  if (I.H != 1 || I.W != kClipTok || (I.C != kClipK && !x3)) return fail(c, PC_ERR_FORMAT, "CLIP net input must be 1x257x608");
+  const bool x3 = I.C == 2 * kpad;
+  if (I.H != 1 || I.W != tok || (I.C != kpad && !x3))
+    return fail(c, PC_ERR_FORMAT, "CLIP net input must be 1 x tokens x padded patch columns of its geometry (1x257x608 at 224 / 14)");
   if (x3 ? (!net->in_centered || net->f32 || I.split) : net->in_centered)
-    return fail(c, PC_ERR_FORMAT, "CLIP net input: 1x257x1216 centred on an f16 net (f16x3 tower) or 1x257x608 normalised");
-  const size_t need = (size_t)net->max_batch * kClipTok * I.C * (net->f32 ? 4 : 2);
+    return fail(c, PC_ERR_FORMAT, "CLIP net input: doubled rows centred on an f16 net (f16x3 tower, 1x257x1216 at 224 / 14) or normalised rows");
+  const size_t need = (size_t)net->max_batch * tok * I.C * (net->f32 ? 4 : 2);
   if (net->prep_bytes < need) {
     if (net->prep) HIPCHK(c, hipFree(net->prep));
     HIPCHK(c, hipMalloc(&net->prep, need));
     net->prep_bytes = need;
   }
-  int rc = pc_clip_prep(c, net->f32 ? PC_PREC_F32 : (x3 ? PC_PREC_F16X3 : PC_PREC_F16), h, n, net->prep);
+  int rc = pc_clip_prep_geom(c, net->f32 ? PC_PREC_F32 : (x3 ? PC_PREC_F16X3 : PC_PREC_F16), side, patch, h, n, net->prep);
   if (rc) return rc;
   rc = pc_net_run(net, net->prep, n);
   if (rc) return rc;
@@ -2548,6 +2573,10 @@ extern "C" int pc_clip_embed(pc_net* net, const pc_crop_desc* h, int n, float* f
   if (!(O.is_f32 || net->f32) || O.H * O.W != 1) return fail(c, PC_ERR_FORMAT, "CLIP output must be f32 [1][1][dim]");
   HIPCHK(c, embed_l2_launch((const float*)tensor_ptr(net, net->outs[0]), O.cs, n, O.C, 1e-12f, feat, c->stream));
   return PC_OK;
+}
+
+extern "C" int pc_clip_embed(pc_net* net, const pc_crop_desc* h, int n, float* feat) {
+  return pc_clip_embed_geom(net, 224, 14, h, n, feat);
 }
 
 extern "C" int pc_l2_normalize(pc_ctx* c, const float* e, int ld, int n, int dim, float eps, float* out) {

@@ -384,8 +384,16 @@ __global__ __launch_bounds__(256) void mha_tokens(AttnParams p) {
   }
 }
 
-hipError_t attention_launch(int f32, const AttnParams& p, int head_dim, hipStream_t s) {
-  if (head_dim != ATT_D || p.T > ATT_TMAX || p.T <= 0 || p.qcs % 8 || p.heads <= 0) return hipErrorInvalidValue;
+// pc_attn.hip: the streaming forms (K and V in LDS tiles: any T; head dims 64 and 80)
+hipError_t attention_stream_launch(int f32, const AttnParams& p, int head_dim, hipStream_t s);
+
+bool attention_head_dim_ok(int head_dim) { return head_dim == 64 || head_dim == 80; }
+
+// head dim 64 with T <= 272 runs mha_tokens (all keys of a head resident in LDS) unless the net
+// was created with PERSON_CAPTURE_AMD_ATTN=stream (stream_form); every other shape streams
+hipError_t attention_launch(int f32, const AttnParams& p, int head_dim, int stream_form, hipStream_t s) {
+  if (stream_form || head_dim != ATT_D || p.T > ATT_TMAX) return attention_stream_launch(f32, p, head_dim, s);
+  if (p.T <= 0 || p.qcs % 8 || p.heads <= 0) return hipErrorInvalidValue;
   const int nqb = (p.T + ATT_Q - 1) / ATT_Q;
   dim3 grid((unsigned)(p.N * p.heads * nqb));
   const bool sp = p.qlo != 0;

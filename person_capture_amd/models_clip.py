@@ -14,10 +14,11 @@ seeded with open_clip's own init scheme (VisionTransformer.init_parameters std v
 Device program (compile_clip_vit): tokens are the pixels of a 1 x 257 image, so
 every linear layer is a 1x1 implicit-GEMM conv on the MFMA engine with its bias,
 GELU and residual add fused in the epilogue; the patch embedding is a 1x1 conv over
-the patch matrix the preprocessing kernel writes ([257][608]: 14*14*3 = 588 columns
-padded to 608, token 0 zero), the class/positional embedding is the additive table of
+the patch matrix the preprocessing kernel writes ([257][608] for ViT-L/14: 14*14*3 = 588
+columns padded to 608, token 0 zero; [T][cpad(3 patch^2)] with T = (image/patch)^2 + 1 for the
+other towers of the family), the class/positional embedding is the additive table of
 the ln_pre LayerNorm op, attention is OP_ATTENTION, and the final projection is a 1x1
-conv with stride 257 that reads only the class token of every image.
+conv with stride T that reads only the class token of every image.
 compile_clip_vit(split=True) builds the f16x3 form of the same program.
 """
 from __future__ import annotations
@@ -37,6 +38,26 @@ CLIP_CFGS = {
     # reduced-depth towers for parity tests (same kernels and shapes per layer)
     "ViT-L-14-d2": dict(width=1024, layers=2, heads=16, mlp=4096, out=768, patch=14, image=224),
     "ViT-tiny-14": dict(width=128, layers=2, heads=2, mlp=512, out=64, patch=14, image=224),
+    # the rest of the OpenCLIP ViT family this build runs (rows as in open_clip's model_configs)
+    "ViT-B-32": dict(width=768, layers=12, heads=12, mlp=3072, out=512, patch=32, image=224),
+    "ViT-L-14-336": dict(width=1024, layers=24, heads=16, mlp=4096, out=768, patch=14, image=336),
+    "ViT-H-14": dict(width=1280, layers=32, heads=16, mlp=5120, out=1024, patch=14, image=224),
+    "ViT-B-16-d2": dict(width=768, layers=2, heads=12, mlp=3072, out=512, patch=16, image=224),
+    "ViT-B-32-d2": dict(width=768, layers=2, heads=12, mlp=3072, out=512, patch=32, image=224),
+    "ViT-L-14-336-d2": dict(width=1024, layers=2, heads=16, mlp=4096, out=768, patch=14, image=336),
+    "ViT-H-14-d2": dict(width=1280, layers=2, heads=16, mlp=5120, out=1024, patch=14, image=224),
+    "ViT-tiny-16": dict(width=128, layers=2, heads=2, mlp=512, out=64, patch=16, image=224),
+    "ViT-tiny-32": dict(width=128, layers=2, heads=2, mlp=512, out=64, patch=32, image=224),
+    "ViT-tiny-h80": dict(width=160, layers=2, heads=2, mlp=640, out=64, patch=14, image=224),
+}
+# geometry the preprocessing and attention kernels cover (pc_clip.hip, pc_attn.hip)
+CLIP_PATCHES = (14, 16, 32)
+CLIP_IMAGES = (224, 336)
+CLIP_HEAD_DIMS = (64, 80)
+# towers of the family that are out of scope: head dims 88 / 104, and the QuickGELU activation
+_UNSUPPORTED = {
+    "ViT-g-14": "its head dim is 88; the attention kernels cover 64 and 80",
+    "ViT-bigG-14": "its head dim is 104; the attention kernels cover 64 and 80",
 }
 LN_EPS = 1e-5
 # open_clip OPENAI_DATASET_MEAN / OPENAI_DATASET_STD (RGB), as pc_clip.hip normalises
@@ -45,11 +66,19 @@ CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 def clip_cfg(name: str) -> dict:
+    if name in _UNSUPPORTED:
+        raise RuntimeError(f"ReID model '{name}' is not part of this MI355X build: {_UNSUPPORTED[name]}")
+    if name.endswith("-quickgelu"):
+        raise RuntimeError(f"ReID model '{name}' is not part of this MI355X build: the QuickGELU variants "
+                           "are not implemented (the MLP epilogue is the exact GELU)")
     if name not in CLIP_CFGS:
-        raise RuntimeError(f"ReID model '{name}' is not part of this MI355X build (have: {sorted(CLIP_CFGS)})")
+        raise RuntimeError(f"ReID model '{name}' is not part of this MI355X build (have: {sorted(CLIP_CFGS)}; "
+                           "ViT-g-14, ViT-bigG-14 and the -quickgelu variants are out of scope)")
     c = dict(CLIP_CFGS[name])
-    if c["patch"] != 14 or c["image"] != 224:
-        raise RuntimeError(f"ReID model '{name}': only 14-pixel patches at 224 are implemented")
+    if c["patch"] not in CLIP_PATCHES or c["image"] not in CLIP_IMAGES or c["image"] % c["patch"]:
+        raise RuntimeError(f"ReID model '{name}': patches of {CLIP_PATCHES} pixels at {CLIP_IMAGES} are implemented")
+    if c["width"] % c["heads"] or c["width"] // c["heads"] not in CLIP_HEAD_DIMS:
+        raise RuntimeError(f"ReID model '{name}': head dims {CLIP_HEAD_DIMS} are implemented")
     return c
 
 

@@ -8,7 +8,7 @@ can be shorter than the input), ``[]`` for an empty list.
 
 Per call the reference converts every crop on the CPU (cvtColor, PIL, open_clip
 preprocess), stacks them, copies the batch to the GPU and runs encode_image in fp32.
-Here one C-ABI call (pc_clip_embed) does it all on the device: the Pillow bicubic
+Here one C-ABI call (pc_clip_embed_geom) does it all on the device: the Pillow bicubic
 resample + centre crop + normalise kernel writes the ViT patch matrix, the image
 tower runs as MFMA 1x1 convs + LayerNorm/attention kernels, and F.normalize finishes.
 
@@ -58,7 +58,9 @@ class ClipEngine:
         # PC_PREC_F16X3: the split program on an f16 net (f32-class embeddings on f16 MFMA)
         self.program = models_clip.compile_clip_vit(params, name, split=precision == PC_PREC_F16X3)
         self.net = Net(ctx, self.program.serialize(), precision=net_precision(precision), max_batch=max_batch)
-        self.dim = models_clip.clip_cfg(name)["out"]
+        cfg = models_clip.clip_cfg(name)
+        self.dim = cfg["out"]
+        self.side, self.patch = cfg["image"], cfg["patch"]
 
     @property
     def flops_per_image(self) -> float:
@@ -72,14 +74,15 @@ class ClipEngine:
         arr = (CropDesc * n)()
         for i, (ptr, H, W, rs) in enumerate(crops):
             arr[i].d_src, arr[i].H, arr[i].W, arr[i].row_stride = int(ptr), int(H), int(W), int(rs)
-        check(self.ctx.lib.pc_clip_embed(self.net.handle, arr, n, C.c_void_p(int(d_out))), self.ctx.handle,
-              "clip_embed")
+        check(self.ctx.lib.pc_clip_embed_geom(self.net.handle, self.side, self.patch, arr, n, C.c_void_p(int(d_out))),
+              self.ctx.handle, "clip_embed")
 
 
 class ReIDEmbedder:
     """
     Body embedding via an OpenCLIP ViT image tower on the MI355X.
-    Defaults to ViT-L-14; returns L2-normalized embeddings as np.float32.
+    Defaults to ViT-L-14; returns L2-normalized embeddings as np.float32. model_name: ViT-B-32,
+    ViT-B-16, ViT-L-14, ViT-L-14-336 or ViT-H-14 (models_clip.CLIP_CFGS).
 
     PERSON_CAPTURE_AMD_REID_PRECISION picks the tower's arithmetic: f32 (default, as the
     reference), f16 (throughput, cosine >= 0.99 only) or f16x3 (f32 class on the f16 matrix
