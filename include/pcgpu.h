@@ -206,6 +206,12 @@ int pc_net_stats(pc_net* net, double* h_flops_per_image, int32_t* h_launches);
  * are used, *h_images_per_round = images one round of workgroups covers (the CU count).
  * (No reference counterpart: a scheduling hint for FaceEmbedder's ArcFace batch quantum.) */
 int pc_net_chain_info(pc_net* net, int32_t* h_min_batch, int32_t* h_images_per_round);
+/* the chained conv_hxi launches a plan would make (host logic only, no device): ops = n_ops x 32 program
+ * op words, eligible[i] != 0 marks the ops the plan runs on the one-image-per-workgroup f16x3 forms,
+ * outs the net's output tensors, cap the layers per launch (<= 0: no cap). Writes up to max_runs
+ * (first op, layers) pairs and returns the number of launches. (No reference counterpart.) */
+int pc_plan_hxi_runs(const int32_t* h_ops, int n_ops, const int32_t* h_eligible, const int32_t* h_outs, int n_outs,
+                     int cap, int32_t* h_runs, int max_runs);
 /* the batch from which the chains run (<= 0: never). A chain workgroup needs a whole CU's
  * LDS, so a net that shares the device with another stream's kernels (FaceEmbedder's embed
  * stream beside SCRFD) runs faster per-conv: measured C3 1925 vs 1705 frames/s. */

@@ -113,6 +113,8 @@ SIGNATURES = {
     "pc_frame_stage": ([_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int], _I),
     "pc_net_chain_info": ([_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], _I),
     "pc_net_set_chain_min_batch": ([_P, C.c_int32], _I),
+    "pc_plan_hxi_runs": ([C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I,
+                          C.POINTER(C.c_int32), _I], _I),
     "pc_net_set_graph": ([_P, _I], _I),
     "pc_net_set_graph_max_batch": ([_P, C.c_int32], _I),
     "pc_net_profile": ([_P, _I], _I),

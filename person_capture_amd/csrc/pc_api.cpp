@@ -31,7 +31,9 @@ hipError_t conv_halo_launch(int f32, int cfg, const ConvParams& p, hipStream_t s
 hipError_t conv_fast_launch(int f32, int rowb, int cfg, const ConvParams& p, hipStream_t s);
 hipError_t conv_hx_launch(const ConvParams& p, hipStream_t s);
 hipError_t conv_hxg_launch(const ConvParams& p, int small, hipStream_t s);
-hipError_t conv_hxi_launch(const ConvParams& p, int small, hipStream_t s);
+hipError_t conv_hxi_launch(const ConvParams& p, int small, int occ1_28, hipStream_t s);
+int conv_hxi_chain_ok(const ConvParams& p);
+hipError_t conv_hxi_chain_launch(const void* d_layers, int nl, int HW, int N, hipStream_t s);
 int conv_fast_num_cfgs();
 constexpr int kFastSmallCfg0 = 15, kFastSmallCfg1 = 19;   // conv_fast tiles 15..19: small-batch plans only
 int conv_fast_tile(int cfg, int* bc, int* bp);
@@ -596,6 +598,20 @@ struct ChainPlan {
   double flops_per_image = 0.0;
 };
 
+// One chained conv_hxi launch (pc_conv_hxi.hip conv_hxi_chain): ops [first, first + nl) of the program,
+// each on the one-image-per-workgroup split form (plan hx 3 or 6) in the plan class it belongs to
+struct HxiRun {
+  int first = -1, nl = 0, hw = 0;
+  size_t param_off = 0;           // its ConvParams[nl] in the class's device array (elements)
+  double flops_per_image = 0.0;
+};
+// the chained launches of one plan class
+struct HxiRuns {
+  std::vector<HxiRun> runs;
+  std::vector<int> at;            // op index -> run id (first op of a run) or -1
+  void* d_params = nullptr;       // ConvParams of every run's layers, uploaded once
+};
+
 struct pc_net {
   pc_ctx* ctx = nullptr;
   int f32 = 0;
@@ -617,6 +633,15 @@ struct pc_net {
   std::vector<ChainPlan> chains;
   std::vector<int> chain_at;      // op index -> chain id (first op of a chain) or -1
   int chain_min_batch = 32;       // PC_CHAIN_MIN overrides (tuning)
+  // chained conv_hxi launches (PC_CONV_HXI bit 6), kept apart from `chains` (pc_net_chain_info counts the
+  // resident f16 chains only): [0] the max-batch plans, [1 + c] plan class c
+  std::vector<HxiRuns> hxi_runs;
+  // layers per chained launch, 0: no cap (PC_HXI_CHAIN_MAX at create). A chained launch holds every CU at one
+  // workgroup for its whole length, and the detection stream's kernels wait behind it: C3 interleaved on one
+  // box, frames/s (4 runs each): per-layer 1032, cap 2 1040, 4 1047, 8 1049, 16 1048, none 1037
+  // (profiles/r07a_hxi_chain_cap_sweep.txt)
+  int hxi_chain_max = 8;
+  int hxi28_occ1 = 0;             // PC_HXI28_OCC=1 at create: the 28x28 split form at one workgroup per CU
   int attn_stream = 0;            // PERSON_CAPTURE_AMD_ATTN=stream at create: pc_attn.hip for every attention shape
   std::vector<const float*> host_arrays;   // program arrays, valid during pc_net_create only
   void* stem_col = nullptr;   // im2col scratch shared by the stems
@@ -677,6 +702,9 @@ static unsigned tensor_zero_off(const pc_net* n, int t) {
 }
 
 static const int kNumConvCfgs = 14;   // pc_conv.hip launch_rowb
+// PC_CONV_HXI's default: every conv_hxi shape but plain f16 14x14x256 (bit 2, which the resident chain
+// beats), and the chained launches of the one-image split forms (bit 6, plan_hxi_runs)
+static const int kHxiDefaultMask = 123;
 
 // K-row width of every f16c8 conv plan (64: a 32-channel K tile and a half-zero block-scaled MFMA;
 // 128: 64 channels and a full one)
@@ -940,13 +968,14 @@ static int plan_conv(pc_net* n, const NetOp& op, ConvPlan& pl, long long plan_ba
     // batches that give every CU a workgroup (plans for >= 192 / 64 images): bit-identical to the fused
     // tiles the smaller plan classes run (same K order, MFMA order and epilogue arithmetic).
     // PC_CONV_HXI is a mask of the shapes it takes: bit 0 14x14x256, bit 1 28x28x128 (f16x3), bits 2 / 3 the
-    // same shapes of plain f16 nets, bit 4 the f16x3 7x7x512, bit 5 the small-batch forms (default 59: all but plain 14x14x256, which the
-    // resident chain beats). ArcFace-x3
+    // same shapes of plain f16 nets, bit 4 the f16x3 7x7x512, bit 5 the small-batch forms, bit 6 runs of
+    // the one-image split forms (14x14x256, 7x7x512) as chained launches (plan_hxi_runs; default 123: all but
+    // plain 14x14x256, which the resident chain beats). ArcFace-x3
     // b256 per layer, interleaved on one box: 28x28x128 187.5 vs 224.2 us on the 128x256 WG tile,
     // 14x14x256 149.3 vs 151.5 on the 256x224 one; C3 962 vs 930 frames/s with the embed quantum at 128
     // faces (256 rows = one round of one-image workgroups; at 383 rows, 1.5 rounds, 876: the quantum
     // follows, face_embedder.py), profiles/r06e_*
-    const int hxi_mask = getenv("PC_CONV_HXI") ? atoi(getenv("PC_CONV_HXI")) : 59;
+    const int hxi_mask = getenv("PC_CONV_HXI") ? atoi(getenv("PC_CONV_HXI")) : kHxiDefaultMask;
     // plain f16 nets (BASELINE C2's fp16 ArcFace): bits 2 / 3 = 14x14x256 / 28x28x128 (tap-major K: the
     // plain tiles' and the resident chain's order, bit-identical). f16 ArcFace b256, one box (r06m):
     // 28x28x128 72.8 us/launch vs 94.0 on tile cfg 14 (C2 f16 7.64 vs 8.17 ms); 14x14x256 65 us x 58 =
@@ -1197,6 +1226,140 @@ static int plan_chains(pc_net* n) {
     n->chain_at[i] = (int)n->chains.size();
     n->chains.push_back(ch);
     i += 2 * ch.nblk;
+  }
+  return PC_OK;
+}
+
+// Chained conv_hxi launches (pc_conv_hxi.hip conv_hxi_chain): the launches that cover the ops marked in
+// `elig` (the convs a plan class runs on the one-image-per-workgroup split forms), as (first op, layers)
+// pairs in program order. A run is a maximal stretch of consecutive marked ops in which
+//  * each op's one input is the previous op's output, and a residual is a tensor written earlier in the
+//    program (inside the run or before it) - so within a launch a workgroup reads only what it wrote itself;
+//  * no tensor written inside the run, but the last op's, is read by an op outside it (or is a net output):
+//    the run ends where such a tensor is written (IResNet: at a block's conv2, never at a conv1).
+// A run of L layers is then cut into launches of at most `cap` layers (cap <= 0: one launch); these cuts
+// fall anywhere - a kernel boundary orders the launches like the per-layer ones.
+// Pure host logic over the program's op words (NetOp::w), exported for tests/test_hxi_runs_cpu.py.
+static void find_hxi_runs(const int32_t* ops, int nops, const int32_t* elig, const int32_t* outs, int nouts,
+                          int cap, std::vector<std::pair<int, int>>& launches) {
+  launches.clear();
+  auto W = [&](int i) { return ops + (size_t)i * 32; };
+  int nt = 0;
+  auto reads = [&](int i, auto&& fn) {
+    const int32_t* w = W(i);
+    if (w[0] == OP_CONV) {
+      for (int sg = 0; sg < w[2] && sg < 2; ++sg) fn(w[3 + 5 * sg]);
+      if (w[21] >= 0) fn(w[21]);
+    } else {
+      fn(w[2]);
+    }
+  };
+  for (int i = 0; i < nops; ++i) {
+    nt = std::max(nt, W(i)[1] + 1);
+    reads(i, [&](int t) { nt = std::max(nt, t + 1); });
+  }
+  for (int k = 0; k < nouts; ++k) nt = std::max(nt, outs[k] + 1);
+  const int kNever = -1, kAlways = 1 << 30;
+  std::vector<int> last_use(nt, kNever), producer(nt, kNever);
+  for (int i = 0; i < nops; ++i) {
+    reads(i, [&](int t) { if (t >= 0) last_use[t] = std::max(last_use[t], i); });
+    if (W(i)[1] >= 0) producer[W(i)[1]] = i;
+  }
+  for (int k = 0; k < nouts; ++k) if (outs[k] >= 0) last_use[outs[k]] = kAlways;
+  auto res_ok = [&](int i) { const int r = W(i)[21]; return r < 0 || producer[r] < i; };
+  auto follows = [&](int i) {   // op i continues a run that holds op i - 1
+    const int32_t* w = W(i);
+    return elig[i] && w[0] == OP_CONV && w[2] == 1 && w[3] == W(i - 1)[1] && res_ok(i);
+  };
+  for (int f = 0; f < nops;) {
+    if (!elig[f] || W(f)[0] != OP_CONV || W(f)[2] != 1 || !res_ok(f)) { ++f; continue; }
+    int e = f;
+    while (e + 1 < nops && follows(e + 1)) ++e;
+    // the longest prefix [f, j] whose inner tensors are all read for the last time inside it
+    int j = e;
+    for (; j > f; --j) {
+      bool ok = true;
+      for (int i = f; i < j && ok; ++i) ok = last_use[W(i)[1]] <= j;
+      if (ok) break;
+    }
+    const int L = j - f + 1, step = cap > 0 ? cap : L;
+    for (int o = 0; o < L; o += step) launches.emplace_back(f + o, std::min(step, L - o));
+    f = j + 1;
+  }
+}
+
+extern "C" int pc_plan_hxi_runs(const int32_t* ops, int n_ops, const int32_t* eligible, const int32_t* outs,
+                                int n_outs, int cap, int32_t* runs, int max_runs) {
+  if (!ops || !eligible || n_ops < 0 || (n_outs > 0 && !outs) || (max_runs > 0 && !runs)) return -PC_ERR_ARG;
+  std::vector<std::pair<int, int>> l;
+  find_hxi_runs(ops, n_ops, eligible, outs, n_outs, cap, l);
+  for (size_t k = 0; k < l.size() && (int)k < max_runs; ++k) {
+    runs[2 * k] = l[k].first;
+    runs[2 * k + 1] = l[k].second;
+  }
+  return (int)l.size();
+}
+
+static void conv_params(pc_net* n, size_t i, const ConvPlan& pl, int N, ConvParams& p);
+
+// The chained launches of every plan class (PC_CONV_HXI bit 6): see find_hxi_runs. The layers' kernel
+// parameters do not depend on the batch (the kernel takes it from its grid), so each class's array is
+// built and uploaded here, once.
+static int plan_hxi_runs(pc_net* n) {
+  n->hxi_runs.clear();
+  if (const char* e = getenv("PC_HXI28_OCC")) n->hxi28_occ1 = atoi(e) == 1;
+  if (const char* e = getenv("PC_HXI_CHAIN_MAX")) n->hxi_chain_max = std::max(0, atoi(e));
+  const int hxi_mask = getenv("PC_CONV_HXI") ? atoi(getenv("PC_CONV_HXI")) : kHxiDefaultMask;
+  // (PC_CONV_DBG strips phases of the per-layer kernels: phase splits measure those)
+  if (n->f32 || !(hxi_mask & 64) || getenv("PC_CONV_DBG")) return PC_OK;
+  const int nops = (int)n->ops.size();
+  std::vector<int32_t> words((size_t)nops * 32), elig(nops);
+  for (int i = 0; i < nops; ++i) memcpy(&words[(size_t)i * 32], n->ops[i].w, sizeof(n->ops[i].w));
+  std::vector<int32_t> outs(n->outs.begin(), n->outs.end());
+  n->hxi_runs.resize(1 + n->plans_cls.size());
+  for (size_t k = 0; k < n->hxi_runs.size(); ++k) {
+    const std::vector<ConvPlan>& plans = k ? n->plans_cls[k - 1] : n->plans;
+    HxiRuns& R = n->hxi_runs[k];
+    R.at.assign(nops, -1);
+    std::vector<ConvParams> params(nops);
+    bool any = false;
+    for (int i = 0; i < nops; ++i) {
+      elig[i] = 0;
+      const int* w = n->ops[i].w;
+      if (w[0] != OP_CONV || (plans[i].hx != 3 && plans[i].hx != 6) || plans[i].splitk != 1) continue;
+      // every tensor a layer touches lives in a buffer and has the map's geometry (H W cs elements per image), so
+      // tensors that share a buffer overlap image by image only - a workgroup's layers never touch another
+      // image's bytes, whichever layer the other workgroups are at
+      const NetTensor &X = n->tens[w[3]], &Y = n->tens[w[1]];
+      bool ok = X.buf >= 0 && Y.buf >= 0 && X.split && Y.split && X.H == Y.H && X.W == Y.W && X.cs == Y.cs;
+      if (ok && w[21] >= 0) {
+        const NetTensor& T = n->tens[w[21]];
+        ok = T.buf >= 0 && T.H == Y.H && T.W == Y.W && T.cs == Y.cs;
+      }
+      if (!ok) continue;
+      conv_params(n, i, plans[i], 0, params[i]);
+      elig[i] = conv_hxi_chain_ok(params[i]);
+      any = any || elig[i];
+    }
+    if (!any) continue;
+    std::vector<std::pair<int, int>> launches;
+    find_hxi_runs(words.data(), nops, elig.data(), outs.data(), (int)outs.size(), n->hxi_chain_max, launches);
+    std::vector<ConvParams> packed;
+    for (auto& l : launches) {
+      HxiRun r;
+      r.first = l.first;
+      r.nl = l.second;
+      r.hw = n->tens[n->ops[l.first].w[1]].H;
+      r.param_off = packed.size();
+      for (int i = l.first; i < l.first + l.second; ++i) {
+        packed.push_back(params[i]);
+        r.flops_per_image += n->plans[i].flops_per_image;
+      }
+      R.at[l.first] = (int)R.runs.size();
+      R.runs.push_back(r);
+    }
+    HIPCHK(n->ctx, hipMalloc(&R.d_params, packed.size() * sizeof(ConvParams)));
+    HIPCHK(n->ctx, hipMemcpy(R.d_params, packed.data(), packed.size() * sizeof(ConvParams), hipMemcpyHostToDevice));
   }
   return PC_OK;
 }
@@ -1570,6 +1733,7 @@ extern "C" int pc_net_create(pc_ctx* c, const void* prog, size_t nbytes, int pre
   }
   n->host_arrays.clear();
   if (rc == PC_OK) rc = plan_chains(n);
+  if (rc == PC_OK) rc = plan_hxi_runs(n);
   if (rc == PC_OK && stem_col_bytes) {
     if (hipMalloc(&n->stem_col, stem_col_bytes) != hipSuccess) rc = fail(c, PC_ERR_HIP, "stem im2col workspace");
     else hipMemset(n->stem_col, 0, stem_col_bytes);
@@ -1605,6 +1769,7 @@ extern "C" int pc_net_destroy(pc_net* n) {
     if (st.slope) hipFree(st.slope);
   }
   if (n->stem_col) hipFree(n->stem_col);
+  for (auto& R : n->hxi_runs) if (R.d_params) hipFree(R.d_params);
   for (auto& ch : n->chains) {
     if (ch.d_blk) hipFree(ch.d_blk);
     if (ch.d_wpack) hipFree(ch.d_wpack);
@@ -1629,6 +1794,78 @@ static int plan_class(const pc_net* n, int N) {
   for (size_t c = 0; c < n->cls_batch.size(); ++c)
     if (N <= n->cls_batch[c]) return (int)c;
   return -1;
+}
+
+// The kernel parameters of conv op i under plan pl for N images (tensor addresses as they are now: a
+// tensor that is the net input follows pc_net::cur_input)
+static void conv_params(pc_net* n, size_t i, const ConvPlan& pl, int N, ConvParams& p) {
+  pc_ctx* c = n->ctx;
+  const int* w = n->ops[i].w;
+  memset(&p, 0, sizeof(p));
+  const NetTensor& Y = n->tens[w[1]];
+  p.nseg = w[2];
+  const int bke = pl.rowb / (n->f32 ? 4 : 2);
+  int kt = 0;
+  for (int sg = 0; sg < p.nseg; ++sg) {
+    const NetTensor& X = n->tens[w[3 + 5 * sg]];
+    ConvSeg& S = p.seg[sg];
+    S.x = tensor_ptr(n, w[3 + 5 * sg]);
+    S.zero_off = tensor_zero_off(n, w[3 + 5 * sg]);
+    S.H = X.H; S.W = X.W; S.C = X.C; S.cs = X.cs;
+    S.KH = w[4 + 5 * sg]; S.KW = w[5 + 5 * sg]; S.stride = w[6 + 5 * sg]; S.pad = w[7 + 5 * sg];
+    S.cblk = X.C / bke;
+    if (X.c8) S.f8s = (127 - X.e_lo) | ((127 - X.e_hi) << 8);
+    if (X.split && pl.sx) {   // fused split tiles: the hi blocks; lo block = hi block + vwrap
+      S.cblk = S.cblk / 2;
+      S.vwrap = S.cblk;
+      // channel groups of 64 hi channels where they divide the channels (ConvSeg::gt)
+      S.gt = (X.C / 2) % 64 == 0 ? 64 / bke : 1;
+    } else if (X.split) {     // virtual channel blocks [hi, lo, hi] (pc_common.h ConvSeg::vwrap)
+      S.vwrap = S.cblk;
+      S.cblk = S.cblk / 2 * 3;
+    }
+    S.kt = S.KH * S.KW * S.cblk;
+    kt += S.kt;
+  }
+  p.w = n->arrays[w[13]];
+  p.ktot = w[15];
+  p.N = N; p.OH = Y.H; p.OW = Y.W; p.M = N * Y.H * Y.W;
+  p.npad = w[14];
+  p.cout = w[16];
+  p.cwrite = std::min(Y.split ? Y.C / 2 : Y.C, p.npad);
+  p.ysplit = Y.split ? Y.C / 2 : 0;
+  p.y = tensor_ptr(n, w[1]);
+  p.ycs = Y.cs;
+  p.out_f32 = Y.is_f32 && !n->f32 ? 1 : (n->f32 ? 1 : 0);
+  p.bias = w[17] >= 0 ? (const float*)n->arrays[w[17]] : nullptr;
+  p.bias_mode = w[17] >= 0 ? w[18] : 0;
+  p.slope = w[19] >= 0 ? (const float*)n->arrays[w[19]] : nullptr;
+  p.act = w[20];
+  p.res = w[21] >= 0 ? tensor_ptr(n, w[21]) : nullptr;
+  p.res_mode = w[21] >= 0 ? w[22] : 0;
+  if (w[21] >= 0) {
+    const NetTensor& R = n->tens[w[21]];
+    p.rcs = R.cs; p.rH = R.H; p.rW = R.W;
+    p.rsplit = R.split ? R.C / 2 : 0;
+  }
+  p.act_after_res = w[23];
+  p.kt_total = kt;
+  p.sx = pl.sx;
+  p.c8 = pl.c8;
+  p.wf8s = n->wf8s[i];
+  p.wfrag = pl.wg || pl.hx ? n->wfrag[i] : nullptr;
+  if (Y.c8) {
+    p.yc8 = 1;
+    p.ylo_mul = std::ldexp(1.f, Y.e_lo);
+    p.yhi_mul = std::ldexp(1.f, Y.e_hi);
+  }
+  if (w[21] >= 0 && n->tens[w[21]].c8) {
+    p.rc8 = 1;
+    p.rlo_inv = std::ldexp(1.f, -n->tens[w[21]].e_lo);
+  }
+  p.splitk = pl.splitk;
+  p.partial = n->partial;
+  p.zero = c->zero;
 }
 
 static int run_ops(pc_net* n, int N, hipStream_t s) {
@@ -1670,7 +1907,12 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
       i += 2 * ch.nblk - 1;
       continue;
     }
-    ProfRec rec{-1, -1, w[0], w[0] == OP_CONV ? n->plans[i].flops_per_image * N : 0.0, (int)i};
+    const int cls = plan_class(n, N);
+    const HxiRuns* hr = n->hxi_runs.empty() ? nullptr : &n->hxi_runs[cls + 1];
+    const HxiRun* run = hr && !n->calib && !hr->runs.empty() && hr->at[i] >= 0 ? &hr->runs[hr->at[i]] : nullptr;
+    // (a chained conv_hxi launch is one timed record: its first op, its layers' FLOPs, kernel code 300)
+    ProfRec rec{-1, -1, w[0], run ? run->flops_per_image * N : w[0] == OP_CONV ? n->plans[i].flops_per_image * N : 0.0,
+                (int)i, run ? 300 : -1};
     if (prof) {
       if (open_ev >= 0) {
         rec.a = open_ev;
@@ -1679,79 +1921,18 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
         if (rc) return rc;
       }
     }
-    if (w[0] == OP_CONV) {
-      const int cls = plan_class(n, N);
+    if (run) {
+      rec.small = cls;
+      HIPCHK(c, conv_hxi_chain_launch(static_cast<const ConvParams*>(hr->d_params) + run->param_off, run->nl, run->hw, N, s));
+      i += run->nl - 1;
+    } else if (w[0] == OP_CONV) {
       const ConvPlan& pl = cls >= 0 ? n->plans_cls[cls][i] : n->plans[i];
       rec.small = cls;
       ConvParams p;
-      memset(&p, 0, sizeof(p));
-      const NetTensor& Y = n->tens[w[1]];
-      p.nseg = w[2];
-      const int bke = pl.rowb / (n->f32 ? 4 : 2);
-      int kt = 0;
-      for (int sg = 0; sg < p.nseg; ++sg) {
-        const NetTensor& X = n->tens[w[3 + 5 * sg]];
-        ConvSeg& S = p.seg[sg];
-        S.x = tensor_ptr(n, w[3 + 5 * sg]);
-        S.zero_off = tensor_zero_off(n, w[3 + 5 * sg]);
-        S.H = X.H; S.W = X.W; S.C = X.C; S.cs = X.cs;
-        S.KH = w[4 + 5 * sg]; S.KW = w[5 + 5 * sg]; S.stride = w[6 + 5 * sg]; S.pad = w[7 + 5 * sg];
-        S.cblk = X.C / bke;
-        if (X.c8) S.f8s = (127 - X.e_lo) | ((127 - X.e_hi) << 8);
-        if (X.split && pl.sx) {   // fused split tiles: the hi blocks; lo block = hi block + vwrap
-          S.cblk = S.cblk / 2;
-          S.vwrap = S.cblk;
-          // channel groups of 64 hi channels where they divide the channels (ConvSeg::gt)
-          S.gt = (X.C / 2) % 64 == 0 ? 64 / bke : 1;
-        } else if (X.split) {     // virtual channel blocks [hi, lo, hi] (pc_common.h ConvSeg::vwrap)
-          S.vwrap = S.cblk;
-          S.cblk = S.cblk / 2 * 3;
-        }
-        S.kt = S.KH * S.KW * S.cblk;
-        kt += S.kt;
-      }
-      p.w = n->arrays[w[13]];
-      p.ktot = w[15];
-      p.N = N; p.OH = Y.H; p.OW = Y.W; p.M = N * Y.H * Y.W;
-      p.npad = w[14];
-      p.cout = w[16];
-      p.cwrite = std::min(Y.split ? Y.C / 2 : Y.C, p.npad);
-      p.ysplit = Y.split ? Y.C / 2 : 0;
-      p.y = tensor_ptr(n, w[1]);
-      p.ycs = Y.cs;
-      p.out_f32 = Y.is_f32 && !n->f32 ? 1 : (n->f32 ? 1 : 0);
-      p.bias = w[17] >= 0 ? (const float*)n->arrays[w[17]] : nullptr;
-      p.bias_mode = w[17] >= 0 ? w[18] : 0;
-      p.slope = w[19] >= 0 ? (const float*)n->arrays[w[19]] : nullptr;
-      p.act = w[20];
-      p.res = w[21] >= 0 ? tensor_ptr(n, w[21]) : nullptr;
-      p.res_mode = w[21] >= 0 ? w[22] : 0;
-      if (w[21] >= 0) {
-        const NetTensor& R = n->tens[w[21]];
-        p.rcs = R.cs; p.rH = R.H; p.rW = R.W;
-        p.rsplit = R.split ? R.C / 2 : 0;
-      }
-      p.act_after_res = w[23];
-      p.kt_total = kt;
-      p.sx = pl.sx;
-      p.c8 = pl.c8;
-      p.wf8s = n->wf8s[i];
-      p.wfrag = pl.wg || pl.hx ? n->wfrag[i] : nullptr;
-      if (Y.c8) {
-        p.yc8 = 1;
-        p.ylo_mul = std::ldexp(1.f, Y.e_lo);
-        p.yhi_mul = std::ldexp(1.f, Y.e_hi);
-      }
-      if (w[21] >= 0 && n->tens[w[21]].c8) {
-        p.rc8 = 1;
-        p.rlo_inv = std::ldexp(1.f, -n->tens[w[21]].e_lo);
-      }
-      p.splitk = pl.splitk;
-      p.partial = n->partial;
-      p.zero = c->zero;
+      conv_params(n, i, pl, N, p);
       if (const char* e = getenv("PC_CONV_DBG")) p.dbg = atoi(e);
       if (pl.hx >= 3 && pl.hx != 5) {
-        HIPCHK(c, conv_hxi_launch(p, pl.hx >= 7, s));
+        HIPCHK(c, conv_hxi_launch(p, pl.hx >= 7, n->hxi28_occ1, s));
       } else if (pl.hx == 2 || pl.hx == 5) {
         HIPCHK(c, conv_hxg_launch(p, pl.hx == 5, s));
       } else if (pl.hx) {
@@ -1891,6 +2072,10 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
       if (rc) return rc;
       n->recs.push_back(rec);
       open_ev = rec.b;
+      // the other layers of a chained launch: a marker each (code 301, no time, no FLOPs - the launch's record
+      // carries both), so a profiled run still has a record per op
+      for (int k = 1; run && k < run->nl; ++k)
+        n->recs.push_back(ProfRec{rec.b, rec.b, OP_CONV, 0.0, rec.op + k, 301, cls});
     }
   }
   return PC_OK;
@@ -1955,7 +2140,7 @@ extern "C" int pc_net_profile_read(pc_net* n, double* out) {
 }
 
 // Per-record detail of the profiled runs: 6 doubles per record
-// [op index, kind, ms, flops, kernel (100+k fast tile k, 200+v t2d variant v, 300 resident chain, 500 halo-staged f16x3, k halo tile k, -1 igemm), igemm cfg or the conv_fast form: bit 0 fused split, bit 1 register weight fragments, bit 2 128-byte K rows]; returns the count.
+// [op index, kind, ms, flops, kernel (100+k fast tile k, 200+v t2d variant v, 300 resident chain or chained conv_hxi launch, 301 a further layer of the chained launch before it (0 ms, 0 flops), 500 halo-staged f16x3, k halo tile k, -1 igemm), igemm cfg or the conv_fast form: bit 0 fused split, bit 1 register weight fragments, bit 2 128-byte K rows]; returns the count.
 extern "C" int pc_net_profile_ops(pc_net* n, double* out, int max_recs) {
   if (!n || !out) return -PC_ERR_ARG;
   HIPCHK(n->ctx, hipStreamSynchronize(n->ctx->stream));

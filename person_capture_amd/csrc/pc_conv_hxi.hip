@@ -29,8 +29,6 @@
 //    28x28x128, profiles/r06f_hxi28_phase_split.txt).
 #include "pc_conv_common.h"
 
-#include <cstdlib>
-
 namespace pc {
 
 // SPLIT (f16x3): a halo slot holds one 64-channel group's hi and lo halves (256 bytes), staged group by
@@ -79,21 +77,23 @@ struct HxiGeom {
   static_assert(NPASS == 1 || WCH % 2 == 0, "epilogue passes split the channel waves");
 };
 
-template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT = true, int OCC = 1>
-__global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX * OCC + 3) / 4) void conv_hxi(ConvParams p) {
+// One layer for this workgroup's rows: `p` is the launch's kernel argument (conv_hxi) or one entry of a
+// chained launch's layer array (conv_hxi_chain, read through the constant address space - the array is
+// uploaded once at plan time and never written while a kernel runs); N is the batch (the grid).
+template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT, int OCC, class P>
+__device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid, char* smem) {
   using G = HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC>;
   constexpr int NW = G::NW, NT = G::NT, TC = G::TC, TP = G::TP, TPG = G::TPG, NG = G::NG, NKS = G::NKS;
   constexpr int STAGE = G::STAGE, PIECES = G::PIECES, SB = G::SB, NB = G::NB, KPG = G::KPG;
   static_assert(G::SMEM * OCC <= 163840, "LDS for OCC workgroups per CU");
   static_assert(NW <= 16, "waves");
-  __shared__ __attribute__((aligned(16))) char smem[G::SMEM];
-  const ConvSeg& S = p.seg[0];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  auto& S = p.seg[0];
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wch = wave % WCH, wpx = wave / WCH;
   constexpr int RB = HW / ROWS, CB = G::CB;      // row blocks per image, channel blocks per row block
   // (a row block's CB workgroups are consecutive: on one XCD after the remap, sharing its halo in the L2)
-  const int b = xcd_remap(blockIdx.x, p.N * RB * CB);
+  const int b = xcd_remap(blockIdx.x, N * RB * CB);
   const int cb = b % CB, nb = b / CB;
   const int n = nb / RB, r0 = (nb - n * RB) * ROWS;
   const int fr = lane & 15, kg = lane >> 4;
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX * OCC + 3) / 4) void con
   const bool pre_act = !p.act_after_res;
   const bool border = p.bias_mode == BIAS_BORDER9;
   const long long pix0 = (long long)n * HW * HW + r0 * HW;   // the workgroup's first output pixel
-  const int cg = threadIdx.x % CGN, pl0 = threadIdx.x / CGN;
+  const int cg = tid % CGN, pl0 = tid / CGN;
 #pragma unroll
   for (int pass = 0; pass < NPASS; ++pass) {
     const int ch = cb * COUT + pass * PC + cg * 8;
@@ -415,6 +415,47 @@ __global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX * OCC + 3) / 4) void con
   }
 }
 
+template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT = true, int OCC = 1>
+__global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX * OCC + 3) / 4) void conv_hxi(ConvParams p) {
+  __shared__ __attribute__((aligned(16))) char smem[HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC>::SMEM];
+  conv_hxi_layer<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC>(p, p.N, (int)threadIdx.x, smem);
+}
+
+// A run of consecutive layers of the one-image-per-workgroup split forms (14x14x256, 7x7x512) as one
+// launch, grid = N: workgroup n walks image n through layers lp[0 .. nl - 1] (pc_api.cpp plan_hxi_runs:
+// each layer reads the previous one's output, a residual is a tensor written earlier in the run or
+// before the launch - always by this workgroup, as it owns every row and channel of its image). The
+// activations still go out to memory and come back as the next layer's halo; what goes is the kernel
+// boundary: the end-of-kernel drain with nothing computing, the launch gap, the per-layer tail sync -
+// the workgroups drift apart, so one's stores drain under the others' MFMAs. Per-layer code is
+// conv_hxi's, so the bits are the per-layer launches' (tests/test_gpu_hxi_chain.py).
+// Between two layers the workgroup's stores must be visible to its own halo DMA and residual loads:
+// every wave waits for its stores (vmcnt(0)), workgroup-scope release, barrier, workgroup-scope acquire.
+// The waves of a workgroup run on one CU and share its vector L1 (the kernels are not built in
+// threadgroup-split mode), which the stores write through - so workgroup scope needs no L1 invalidate
+// or L2 write-back, and no device-scope flush is needed (LLVM AMDGPUUsage, "Memory Model gfx942":
+// workgroup-scope release / acquire fences in non-tgsplit mode are s_waitcnt only).
+// The barrier also keeps the next layer's first halo stage off the LDS image a slower wave still reads.
+template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX>
+__global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX + 3) / 4) void conv_hxi_chain(const ConvParams* lp, int nl) {
+  __shared__ __attribute__((aligned(16))) char smem[HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, true, 1>::SMEM];
+  typedef const __attribute__((address_space(4))) ConvParams CP;
+  CP* cp = (CP*)lp;
+  for (int l = 0; l < nl; ++l) {
+    if (l) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __syncthreads();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    // (the thread index made opaque per layer: hoisted out of the layer loop, the per-thread offsets
+    // derived from it stay live through the K loop and spill the 14x14 form, 233 registers as it is)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    conv_hxi_layer<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, true, 1>(cp[l], (int)gridDim.x, tid, smem);
+  }
+}
+
 // the instantiated shapes: IResNet's 14x14x256 (one image per workgroup, 8 x 1 waves of 32 channels x
 // 14 rows) and 28x28x128 (7 rows per workgroup, 4 x 2 waves of 32 channels x 7 fragments); plain f16
 // 28x28x128 at two workgroups per CU (its halo stage is 73 KB)
@@ -447,7 +488,7 @@ int conv_hxi_ok(const ConvParams& p) {
          p.wfrag != nullptr && (!split || p.ysplit == C);
 }
 
-hipError_t conv_hxi_launch(const ConvParams& p, int small, hipStream_t s) {
+hipError_t conv_hxi_launch(const ConvParams& p, int small, int occ1_28, hipStream_t s) {
   if (!conv_hxi_ok(p)) return hipErrorInvalidValue;
   const bool split = p.ysplit != 0;
   if (small) {   // (16 workgroups per image; split only)
@@ -464,12 +505,27 @@ hipError_t conv_hxi_launch(const ConvParams& p, int small, hipStream_t s) {
     else hipLaunchKernelGGL((conv_hxi<PC_HXI_14, false, 1>), dim3(p.N), dim3(512), 0, s, p);
   } else {
     // (split: two workgroups per CU, one halo stage each, so one's epilogue runs under the other's MFMAs;
-    // PC_HXI28_OCC=1 the 2-stage form)
-    const bool occ1 = getenv("PC_HXI28_OCC") && atoi(getenv("PC_HXI28_OCC")) == 1;   // (per launch: A/B in one process)
-    if (split && occ1) hipLaunchKernelGGL((conv_hxi<PC_HXI_28, true, 1>), dim3(p.N * 4), dim3(512), 0, s, p);
+    // PC_HXI28_OCC=1 the 2-stage form, read when the net is built: pc_api.cpp)
+    if (split && occ1_28) hipLaunchKernelGGL((conv_hxi<PC_HXI_28, true, 1>), dim3(p.N * 4), dim3(512), 0, s, p);
     else if (split) hipLaunchKernelGGL((conv_hxi<PC_HXI_28, true, 2>), dim3(p.N * 4), dim3(512), 0, s, p);
     else hipLaunchKernelGGL((conv_hxi<PC_HXI_28, false, 2>), dim3(p.N * 4), dim3(512), 0, s, p);
   }
+  return hipGetLastError();
+}
+
+// can a conv be a layer of a chained launch: the split one-image-per-workgroup shapes
+int conv_hxi_chain_ok(const ConvParams& p) {
+  return conv_hxi_ok(p) && p.ysplit != 0 && (p.OH == 14 || p.OH == 7) && p.dbg == 0;
+}
+
+// nl layers (d_layers: ConvParams[nl] on the device, each conv_hxi_chain_ok, all of one map size HW) for
+// N images as one launch
+hipError_t conv_hxi_chain_launch(const void* d_layers, int nl, int HW, int N, hipStream_t s) {
+  if (!d_layers || nl < 1 || N < 1) return hipErrorInvalidValue;
+  const ConvParams* lp = static_cast<const ConvParams*>(d_layers);
+  if (HW == 14) hipLaunchKernelGGL((conv_hxi_chain<PC_HXI_14>), dim3(N), dim3(512), 0, s, lp, nl);
+  else if (HW == 7) hipLaunchKernelGGL((conv_hxi_chain<PC_HXI_7>), dim3(N), dim3(512), 0, s, lp, nl);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -1,0 +1,106 @@
+"""The run finder of the chained conv_hxi launches (pc_api.cpp find_hxi_runs, exported as
+pc_plan_hxi_runs: host logic, no device) on the real IResNet-100 f16x3 program and on hand-made programs.
+
+A run is a stretch of consecutive eligible convs, each reading the previous one's output, whose inner
+tensors are read inside the run only; a cap cuts a run into launches of at most that many layers."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from person_capture_amd import _lib, models
+
+OP_CONV = 1
+
+
+def _runs(ops, elig, outs, cap=0):
+    lib = _lib.load()
+    words = np.ascontiguousarray(np.asarray(ops, np.int32).reshape(len(ops), 32))
+    e = np.ascontiguousarray(np.asarray(elig, np.int32))
+    o = np.ascontiguousarray(np.asarray(outs, np.int32))
+    buf = np.zeros(2 * max(1, len(ops)), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    k = lib.pc_plan_hxi_runs(words.ctypes.data_as(i32p), len(ops), e.ctypes.data_as(i32p), o.ctypes.data_as(i32p),
+                             len(o), cap, buf.ctypes.data_as(i32p), len(ops))
+    assert 0 <= k <= len(ops)
+    return [(int(buf[2 * j]), int(buf[2 * j + 1])) for j in range(k)]
+
+
+def _conv(out, inp, res=-1):
+    """A 3x3 / stride 1 / pad 1 conv's op words (the fields the finder reads: tensors and segment count)."""
+    w = [0] * 32
+    w[0], w[1], w[2], w[3] = OP_CONV, out, 1, inp
+    w[4] = w[5] = 3
+    w[6] = w[7] = 1
+    w[21] = res
+    return w
+
+
+@pytest.fixture(scope="module")
+def r100():
+    P = models.compile_iresnet(models.synth_iresnet(100, seed=0, calibrate=False), 100, split=True)
+    elig = []
+    for w in P.ops:
+        ok = False
+        if w[0] == OP_CONV and w[2] == 1 and w[4] == 3 and w[5] == 3 and w[6] == 1:
+            (H, W_, Ci), (Ho, _, Co) = P.dims(w[3]), P.dims(w[1])
+            ok = H == Ho == W_ and Ci == Co and (H, Ci) in ((14, 256), (7, 512))   # (logical channels)
+        elig.append(int(ok))
+    return P, elig
+
+
+def test_iresnet100_runs(r100):
+    """The 58 14x14x256 and 4 7x7x512 layers are one run each: every layer in between reads its predecessor,
+    a conv2's residual is the previous block's output."""
+    P, elig = r100
+    assert sum(elig) == 62
+    runs = _runs(P.ops, elig, P.outputs)
+    assert sorted(n for _, n in runs) == [4, 58], runs
+    for first, n in runs:
+        assert all(elig[first:first + n]) and (first == 0 or not elig[first - 1])
+        for i in range(first + 1, first + n):
+            assert P.ops[i][3] == P.ops[i - 1][1]
+
+
+@pytest.mark.parametrize("cap,want", [(1, [1] * 62), (3, [3] * 19 + [1] + [3, 1]), (16, [16, 16, 16, 10, 4]),
+                                      (58, [58, 4]), (100, [58, 4])])
+def test_iresnet100_cap(r100, cap, want):
+    P, elig = r100
+    runs = _runs(P.ops, elig, P.outputs, cap)
+    assert [n for _, n in runs] == want
+    covered = [i for first, n in runs for i in range(first, first + n)]
+    assert covered == [i for i, e in enumerate(elig) if e]
+
+
+def test_ineligible_op_splits(r100):
+    P, elig = r100
+    first = elig.index(1)
+    e2 = list(elig)
+    e2[first + 7] = 0
+    runs = _runs(P.ops, e2, P.outputs)
+    # [first, first + 7) has 7 layers: it would end on a conv1 whose block input is read by the conv2
+    # outside it, so the run closes at the conv2 before (6 layers), and the seventh is a launch of its own
+    assert runs[:2] == [(first, 6), (first + 6, 1)], runs
+    assert runs[2][0] == first + 8
+
+
+def test_tensor_read_from_outside_splits():
+    """t1 -> c0 -> t2 -> c1 -> t3 -> c2 -> t4 -> c3 -> t5, and a later op outside reads t3: the run must
+    end where t3 is written. Without that reader the four convs are one run."""
+    chain = [_conv(2, 1), _conv(3, 2), _conv(4, 3), _conv(5, 4)]
+    tail = _conv(6, 5)
+    assert _runs(chain + [tail], [1, 1, 1, 1, 0], [6]) == [(0, 4)]
+    late = _conv(6, 5, res=3)       # not eligible, reads t3 as its residual
+    assert _runs(chain + [late], [1, 1, 1, 1, 0], [6]) == [(0, 2), (2, 2)]
+    # t3 as a net output is read from outside as well
+    assert _runs(chain + [tail], [1, 1, 1, 1, 0], [6, 3]) == [(0, 2), (2, 2)]
+    # an inner residual (c3 adds t3) keeps the run whole: its reader is inside
+    inner = chain[:3] + [_conv(5, 4, res=3)]
+    assert _runs(inner + [tail], [1, 1, 1, 1, 0], [6]) == [(0, 4)]
+
+
+def test_input_must_be_previous_output():
+    """c1 reads t1 again, not c0's output: two runs."""
+    ops = [_conv(2, 1), _conv(3, 1), _conv(4, 3)]
+    assert _runs(ops, [1, 1, 1], [2, 4]) == [(0, 1), (1, 2)]
+    assert _runs(ops, [0, 0, 0], [4]) == []
