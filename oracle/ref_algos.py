@@ -318,9 +318,11 @@ def yolo_letterbox(frame: np.ndarray, imgsz: int = 640, stride: int = 32) -> Tup
 
 
 def yolo_postprocess(heads: Sequence[np.ndarray], conf: float, iou: float, max_det: int, Hp: int, Wp: int,
-                     H0: int, W0: int, nk: int = 0):
+                     H0: int, W0: int, nk: int = 0, max_nms: Optional[int] = 30000):
     """Detect inference decode + ops.non_max_suppression(classes=[0]) + ops.scale_boxes for one
-    image. heads: per stride [H][W][64+nc(+nk)] f32. Returns [k][5] (x1, y1, x2, y2, conf); with
+    image. heads: per stride [H][W][64+nc(+nk)] f32. Only the max_nms best candidates (score
+    descending, then anchor ascending) enter the NMS (ops.non_max_suppression's max_nms = 30000;
+    None: all of them). Returns [k][5] (x1, y1, x2, y2, conf); with
     nk > 0 (Pose head, kpt ndim 3) also the keypoints [k][nk/3][3] of the kept boxes:
     Pose.kpts_decode (x = (raw * 2 + anchor - 0.5) * stride, sigmoid visibility), carried
     through the NMS, ops.scale_coords (unrounded pad, then /gain, clip) and Results'
@@ -366,6 +368,8 @@ def yolo_postprocess(heads: Sequence[np.ndarray], conf: float, iou: float, max_d
             cand.append((f32(cx - hw_), f32(cy - hh_), f32(cx + hw_), f32(cy + hh_), score[a], aoff + int(a), kp))
         aoff += h * w
     cand.sort(key=lambda c: (-float(c[4]), c[5]))
+    if max_nms is not None:
+        cand = cand[:max_nms]
     kept = []
     supp = [False] * len(cand)
     for i, ci in enumerate(cand):
@@ -407,4 +411,104 @@ def yolo_postprocess(heads: Sequence[np.ndarray], conf: float, iou: float, max_d
             if v < f32(0.5):
                 x = y = f32(0)
             kpts[r, q] = (x, y, v)
+    return out, kpts
+
+
+def _yolo_class0(heads: Sequence[np.ndarray], conf: float, nk: int):
+    """Per level: (flat f32 head, class-0 candidates' anchor rows, all scores)."""
+    f32 = np.float32
+    out = []
+    for hd in heads:
+        h, w, _ = hd.shape
+        flat = hd.reshape(h * w, -1).astype(f32)
+        cls = flat[:, 64:flat.shape[1] - nk]
+        j = np.argmax(cls, axis=1)
+        best = cls[np.arange(h * w), j]
+        score = (1.0 / (1.0 + np.exp(-best.astype(np.float64)))).astype(f32)
+        out.append((flat, np.nonzero((j == 0) & (score > f32(conf)))[0], score))
+    return out
+
+
+def yolo_candidate_scores(heads: Sequence[np.ndarray], conf: float, nk: int = 0) -> np.ndarray:
+    """The f32 scores of every class-0 candidate above conf, descending, before any max_nms cut:
+    its length is the candidate count the device reports."""
+    s = np.concatenate([score[keep] for _, keep, score in _yolo_class0(heads, conf, nk)])
+    return -np.sort(-s, kind="stable")
+
+
+def yolo_postprocess_vec(heads: Sequence[np.ndarray], conf: float, iou: float, max_det: int, Hp: int, Wp: int,
+                         H0: int, W0: int, nk: int = 0, max_nms: Optional[int] = 30000):
+    """yolo_postprocess with numpy over the anchors: the same f32 operations in the same order
+    (DFL bins accumulated one by one, the greedy NMS row by row with only its inner loop
+    vectorised), so the results are equal bit for bit (tests/test_yolo_cpu.py); usable at the
+    tens of thousands of candidates of the heavy canvases."""
+    f32 = np.float32
+    boxes, scores, anchors, kps = [], [], [], []
+    aoff = 0
+    for (flat, keep, score), hd, s in zip(_yolo_class0(heads, conf, nk), heads, (8, 16, 32)):
+        h, w, _ = hd.shape
+        b = flat[keep, :64].reshape(-1, 4, 16)
+        e = np.exp((b - b.max(axis=2, keepdims=True)).astype(np.float64)).astype(f32)
+        ssum = np.zeros(e.shape[:2], f32)
+        for i in range(16):
+            ssum = ssum + e[:, :, i]
+        d = np.zeros(e.shape[:2], f32)
+        for i in range(16):
+            d = d + (e[:, :, i] / ssum) * f32(i)
+        y, x = np.divmod(keep, w)
+        xf, yf, sf = x.astype(f32), y.astype(f32), f32(s)
+        ax, ay = xf + f32(0.5), yf + f32(0.5)
+        x1, y1, x2, y2 = ax - d[:, 0], ay - d[:, 1], ax + d[:, 2], ay + d[:, 3]
+        cx, cy = (x1 + x2) / f32(2) * sf, (y1 + y2) / f32(2) * sf
+        hw_, hh_ = (x2 - x1) * sf / f32(2), (y2 - y1) * sf / f32(2)
+        boxes.append(np.stack([cx - hw_, cy - hh_, cx + hw_, cy + hh_], axis=1).astype(f32))
+        scores.append(score[keep])
+        anchors.append(aoff + keep)
+        if nk:
+            raw = flat[keep, flat.shape[1] - nk:].reshape(-1, nk // 3, 3)
+            kp = np.zeros(raw.shape, f32)
+            kp[:, :, 0] = (raw[:, :, 0] * f32(2.0) + xf[:, None]) * sf
+            kp[:, :, 1] = (raw[:, :, 1] * f32(2.0) + yf[:, None]) * sf
+            kp[:, :, 2] = (1.0 / (1.0 + np.exp(-raw[:, :, 2].astype(np.float64)))).astype(f32)
+            kps.append(kp)
+        aoff += h * w
+    boxes, scores, anchors = np.concatenate(boxes), np.concatenate(scores), np.concatenate(anchors)
+    order = np.lexsort((anchors, -scores.astype(np.float64)))   # score descending, then anchor ascending
+    if max_nms is not None:
+        order = order[:max_nms]
+    B = boxes[order]
+    area = (B[:, 2] - B[:, 0]) * (B[:, 3] - B[:, 1])
+    alive = np.arange(len(order))      # unsuppressed candidates not yet visited, in order
+    kept = []
+    thr = f32(iou)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        while alive.size:
+            i, alive = alive[0], alive[1:]
+            kept.append(i)
+            if len(kept) >= max_det:
+                break
+            ww = np.maximum(np.minimum(B[i, 2], B[alive, 2]) - np.maximum(B[i, 0], B[alive, 0]), f32(0.0))
+            hh = np.maximum(np.minimum(B[i, 3], B[alive, 3]) - np.maximum(B[i, 1], B[alive, 1]), f32(0.0))
+            inter = ww * hh
+            alive = alive[~(inter / ((area[i] + area[alive]) - inter) > thr)]
+    kept = np.asarray(kept, np.int64)
+    from person_capture_amd.models_yolo import scale_geometry   # sizing formulas only
+    gain, px, py = scale_geometry(Hp, Wp, H0, W0)
+    g = f32(gain)
+    K = B[kept]
+    out = np.zeros((len(kept), 5), f32)
+    out[:, 0] = np.minimum(np.maximum((K[:, 0] - f32(px)) / g, f32(0)), f32(W0))
+    out[:, 1] = np.minimum(np.maximum((K[:, 1] - f32(py)) / g, f32(0)), f32(H0))
+    out[:, 2] = np.minimum(np.maximum((K[:, 2] - f32(px)) / g, f32(0)), f32(W0))
+    out[:, 3] = np.minimum(np.maximum((K[:, 3] - f32(py)) / g, f32(0)), f32(H0))
+    out[:, 4] = scores[order][kept]
+    if not nk:
+        return out
+    kx, ky = f32((Wp - W0 * gain) / 2), f32((Hp - H0 * gain) / 2)   # scale_coords: pad not rounded
+    kp = np.concatenate(kps)[order][kept]
+    kpts = np.zeros(kp.shape, f32)
+    kpts[:, :, 0] = np.minimum(np.maximum((kp[:, :, 0] - kx) / g, f32(0)), f32(W0))
+    kpts[:, :, 1] = np.minimum(np.maximum((kp[:, :, 1] - ky) / g, f32(0)), f32(H0))
+    kpts[:, :, 2] = kp[:, :, 2]
+    kpts[kp[:, :, 2] < f32(0.5), :2] = f32(0)
     return out, kpts

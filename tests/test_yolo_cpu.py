@@ -145,3 +145,121 @@ def test_yolo_pose_postprocess_contract():
         x = (raw[q, 0] * 2 + 30) * 8
         y = (raw[q, 1] * 2 + 20) * 8
         assert abs(k[0, q, 0] - x / gain) < 1e-2 and abs(k[0, q, 1] - (y - 12) / gain) < 1e-2
+
+
+# ---------------------------------------------------------------------------
+# yolo_postprocess_vec (the reference of tests/test_gpu_yolo_nms.py) == the scalar oracle, bit for bit
+# ---------------------------------------------------------------------------
+VEC_HP, VEC_WP = 192, 256
+
+
+def _random_heads(seed, nc, nk, box=2.0, quant=None, cls_bias=0.0):
+    """Random head maps of a 192x256 canvas (1008 anchors): DFL logits peaked near bin `box`, class
+    logits normal (quant: rounded to that step, so most scores tie), raw keypoints with both signs
+    of the visibility logit."""
+    rng = np.random.default_rng(seed)
+    heads = []
+    for s in (8, 16, 32):
+        h, w = VEC_HP // s, VEC_WP // s
+        hd = rng.normal(0.0, 1.0, (h, w, 64 + nc + nk)).astype(np.float32)
+        hd[..., :64] -= (0.8 * np.abs(np.arange(16) - box * 8 / s)).astype(np.float32)[np.tile(np.arange(16), 4)]
+        hd[..., 64] += np.float32(cls_bias)       # class 0 (person) against the other classes
+        if quant:
+            hd[..., 64:64 + nc] = np.round(hd[..., 64:64 + nc] / quant) * np.float32(quant)
+        heads.append(hd)
+    return heads
+
+
+def _both(heads, conf, iou, max_det, H0, W0, nk=0, **kw):
+    a = ra.yolo_postprocess(heads, conf, iou, max_det, VEC_HP, VEC_WP, H0, W0, nk=nk, **kw)
+    b = ra.yolo_postprocess_vec(heads, conf, iou, max_det, VEC_HP, VEC_WP, H0, W0, nk=nk, **kw)
+    if nk:
+        assert a[0].dtype == b[0].dtype == np.float32 and a[1].dtype == b[1].dtype == np.float32
+        assert a[0].shape == b[0].shape and a[1].shape == b[1].shape
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        return a
+    assert a.dtype == b.dtype == np.float32 and a.shape == b.shape
+    assert np.array_equal(a, b)
+    return a, None
+
+
+# frame 300x420 on the 192x256 canvas: gain 0.6095, pad (0, 5), clipping at the frame edges
+VEC_FRAME = (300, 420)
+
+
+@pytest.mark.parametrize("nc,nk,conf", [(1, 0, 0.6), (80, 0, 0.5), (1, 15, 0.6), (80, 15, 0.5)])
+def test_yolo_postprocess_vec_equals_scalar(nc, nk, conf):
+    heads = _random_heads(11 + nc + nk, nc, nk, cls_bias=0.0 if nc == 1 else 2.5)
+    g, px, py = my.scale_geometry(VEC_HP, VEC_WP, *VEC_FRAME)
+    assert g not in (0.0, 1.0) and (px, py) != (0, 0)
+    d, k = _both(heads, conf, 0.45, 1000, *VEC_FRAME, nk=nk)
+    n = len(ra.yolo_candidate_scores(heads, conf, nk))
+    print("candidates", n, "kept", len(d))
+    assert n >= 100 and 0 < len(d) < n          # some suppressed
+    assert (d[:, :4] == 0).any() or (d[:, 2] == VEC_FRAME[1]).any() or (d[:, 3] == VEC_FRAME[0]).any()   # clipped
+    if nk:
+        assert (k[..., 2] < 0.5).any() and (k[..., 2] >= 0.5).any()
+
+
+def test_yolo_postprocess_vec_ties():
+    """Class logits on a 0.5 grid: most candidates share their score with another, so the order is
+    decided by the anchor index."""
+    heads = _random_heads(21, 1, 0, quant=0.5)
+    s = ra.yolo_candidate_scores(heads, 0.6)
+    _, counts = np.unique(s, return_counts=True)
+    tied = int(counts[counts > 1].sum())
+    assert len(s) >= 300 and tied >= 0.9 * len(s), (len(s), tied)
+    d, _ = _both(heads, 0.6, 0.45, 1000, *VEC_FRAME)
+    assert np.all(np.diff(d[:, 4]) <= 0) and len(np.unique(d[:, 4])) < len(d)
+
+
+def test_yolo_postprocess_vec_max_det_and_max_nms():
+    heads = _random_heads(31, 1, 15, box=1.0)
+    full, kf = _both(heads, 0.5, 0.45, 1000, *VEC_FRAME, nk=15)
+    assert len(full) > 60
+    for md in (40, 1):
+        d, k = _both(heads, 0.5, 0.45, md, *VEC_FRAME, nk=15)
+        assert len(d) == md and np.array_equal(d, full[:md]) and np.array_equal(k, kf[:md])
+    # max_nms: only the 50 best candidates enter the NMS; None: all of them
+    cut, _ = _both(heads, 0.5, 0.45, 1000, *VEC_FRAME, nk=15, max_nms=50)
+    assert 0 < len(cut) < len(full) and np.array_equal(cut, full[:len(cut)])
+    unc, _ = _both(heads, 0.5, 0.45, 1000, *VEC_FRAME, nk=15, max_nms=None)
+    assert np.array_equal(unc, full)       # below the default 30000 the cut is void
+    assert len(ra.yolo_candidate_scores(heads, 0.5, 15)) > 50
+
+
+def test_yolo_postprocess_vec_empty():
+    heads = _random_heads(41, 1, 15)
+    d, k = _both(heads, 0.9999, 0.45, 40, *VEC_FRAME, nk=15)
+    assert d.shape == (0, 5) and k.shape == (0, 5, 3)
+    assert len(ra.yolo_candidate_scores(heads, 0.9999, 15)) == 0
+
+
+@pytest.mark.parametrize("nkpt", [0, 5])
+def test_head_program_interface_and_knobs(nkpt):
+    """tests/yolo_head_program.py (the net of tests/test_gpu_yolo_nms.py) through the emulator: three
+    heads of 64 + 1 (+ 15) channels at strides 8 / 16 / 32; brightness steers the score, `box` the
+    box size, and the interior anchors of constant 64-px tiles tie exactly."""
+    import yolo_head_program as yh
+    Hp = Wp = 256
+
+    def heads(fr, box):
+        x = np.zeros((1, Hp, Wp, 4), np.float32)
+        x[0, ..., :3] = fr[..., ::-1].astype(np.float32) / np.float32(255)
+        outs = run_program(yh.head_program(Hp, Wp, nkpt, box), x)
+        return [o.permute(0, 2, 3, 1).numpy()[0] for o in outs]
+
+    hn = heads(yh.noise_frame(Hp, Wp, 1), 2.0)
+    assert [h.shape for h in hn] == [(Hp // s, Wp // s, 65 + 3 * nkpt) for s in (8, 16, 32)]
+    nk = 3 * nkpt
+    total = Hp * Wp * 21 // 1024
+    assert len(ra.yolo_candidate_scores(hn, 0.1, nk)) > 0.95 * total
+    assert len(ra.yolo_candidate_scores(heads(yh.dark_frame(Hp, Wp), 2.0), 0.1, nk)) == 0
+    small = ra.yolo_postprocess_vec(hn, 0.1, 0.45, total, Hp, Wp, Hp, Wp, nk=nk)
+    large = ra.yolo_postprocess_vec(heads(yh.noise_frame(Hp, Wp, 1), 8.0), 0.1, 0.45, total, Hp, Wp, Hp, Wp, nk=nk)
+    if nkpt:
+        small, large = small[0], large[0]
+    assert len(small) > 4 * len(large) > 0
+    s = ra.yolo_candidate_scores(heads(yh.tiled_frame(Hp, Wp, 2, lo=32, hi=224), 2.0), 0.0, nk)
+    _, counts = np.unique(s, return_counts=True)
+    assert counts[counts > 1].sum() >= 16 * 25      # 16 tiles, at least 5x5 interior stride-8 anchors each
