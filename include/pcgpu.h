@@ -46,6 +46,11 @@
  *   pc_l2_normalize                    torch.nn.functional.normalize(feats, dim=1) (reid_embedder.py:55)
  *   pc_pil_bicubic_coeffs              Pillow Image.resize(BICUBIC) coefficients inside the open_clip
  *                                      preprocess (reid_embedder.py:49)
+ *   pc_crop_metrics                    the cv2 half of phash64, sharpness_norm, exposure_score
+ *                                      (dataset_curator.py:55-113) and detect_black_borders
+ *                                      (utils.py:152-196), batched; the host finishes them
+ *   pc_sim_matrix                      Fs @ Fs.T of Curator.select (dataset_curator.py:961-977)
+ *   pc_mmr_order                       mmr_select_with_q (dataset_curator.py:211-238)
  */
 #ifndef PCGPU_H
 #define PCGPU_H
@@ -146,6 +151,37 @@ typedef struct pc_crop_desc {
   const uint8_t* d_src;
   int32_t H, W, row_stride, pad_;
 } pc_crop_desc;
+
+/* One crop of the dataset curator's metrics batch (pc_crop_metrics): a BGR u8 image on the device and
+ * the geometry of its two INTER_AREA targets, [0] the <= 256 plane of sharpness_norm (w2 x h2;
+ * the gray plane itself when max(h, w) <= 256) and [1] the 32 x 32 plane of phash64. Per target:
+ * kind (PC_CURATE_COPY: the gray plane is the target; PC_CURATE_FAST: integer ratios isx x isy,
+ * OpenCV's resizeAreaFast; PC_CURATE_AREA: generic tables), and for PC_CURATE_AREA the positions
+ * xs / ys in h_starts of the target's x / y start arrays (ow + 1 / oh + 1 entries, each an index
+ * into h_tabs; destination d's coefficients are h_tabs[start[d] .. start[d + 1])). */
+#define PC_CURATE_COPY 0
+#define PC_CURATE_FAST 1
+#define PC_CURATE_AREA 2
+typedef struct pc_curate_desc {
+  const uint8_t* d_src;
+  int32_t row_stride, w, h;
+  int32_t w2, h2;
+  int32_t kind[2];
+  int32_t isx[2], isy[2];
+  int32_t xs[2], ys[2];
+  int32_t pad_;
+} pc_curate_desc;
+
+/* The per-image record pc_crop_metrics writes at the front of d_out (n records, then the row and
+ * column sums): everything except coef is an exact integer. */
+typedef struct pc_curate_record {
+  uint64_t sum_g2;    /* sum of the <= 256 plane */
+  int64_t sum_lap;    /* sum of its ksize-1 Laplacian (BORDER_REFLECT_101) */
+  uint64_t sum_lap2;  /* sum of the squares */
+  int32_t w2, h2;
+  uint32_t hist[256]; /* of the full-size gray plane */
+  float coef[64];     /* [u][v] 8x8 low-frequency block of the orthonormal DCT-II of the 32 x 32 plane */
+} pc_curate_record;
 
 int pc_abi_version(void);
 
@@ -326,6 +362,35 @@ int pc_l2_normalize(pc_ctx* ctx, const float* d_e, int ld, int n, int dim, float
 int pc_pil_bicubic_coeffs(int in_size, int out_size, int first, int count, int32_t* h_bounds, int32_t* h_kk, int kmax);
 /* torchvision Resize(side) + CenterCrop(side) geometry: h_out4 = resized w, h, crop top, left */
 int pc_clip_geometry(int h, int w, int side, int32_t* h_out4);
+
+/* ---- dataset curator: crop metrics and MMR ranking ---- */
+/* Host only (no context, no device): checks n descriptors (32 <= w, h <= 16384, row_stride >= 3 w,
+ * w2 / h2 = the reference's int(round(w s)), int(round(h s)) with s = 256 / max(h, w) and >= 1, 32 x 32
+ * for target 1, kinds that fit the sizes; anything else PC_ERR_ARG) and lays out the buffers of
+ * pc_crop_metrics. h_off [n][5] byte offsets: [0] gray plane, [1] <= 256 plane, [2] 32 x 32 plane in
+ * d_scratch (pitches: width rounded up to 16; a PC_CURATE_COPY target is the gray plane), [3] the
+ * image's pc_curate_record, [4] its row_sum[h] then col_sum[w] (u32) in d_out. */
+int pc_crop_metrics_layout(const pc_curate_desc* h_imgs, int n, uint64_t* h_off, size_t* h_scratch_bytes,
+                           size_t* h_out_bytes);
+/* The image half of the curator's per-crop metrics for n crops in four launches, stream-ordered:
+ * BGR2GRAY (14-bit coefficients, as pc_face_quality) with histogram, row and column sums (what
+ * exposure_score, dataset_curator.py:101-113, and detect_black_borders, utils.py:152-196, read), the
+ * INTER_AREA planes of sharpness_norm (dataset_curator.py:81-98) and phash64 (dataset_curator.py:55-71),
+ * the Laplacian sums, and the DCT block from the host's cosine table h_dct [8][32] f64
+ * (c_u cos(pi (2 x + 1) u / 64)). Buffers are the caller's, sized and laid out by
+ * pc_crop_metrics_layout; d_out is zeroed here. The host derives the reference's values from the
+ * integers (person_capture_amd/curate.py). */
+int pc_crop_metrics(pc_ctx* ctx, const pc_curate_desc* h_imgs, int n, const pc_area_tab* h_tabs, int n_tabs,
+                    const int32_t* h_starts, int n_starts, const double* h_dct, void* d_scratch, size_t scratch_bytes,
+                    void* d_out, size_t out_bytes);
+/* S = F F^T of Curator.select (dataset_curator.py:961-977; Fs @ Fs.T at :972): d_F [n][dim] f32 rows
+ * (unit or all zero), d_S [n][n] f32. Every element is one fmaf chain over k ascending, so S is
+ * exactly symmetric and two runs give the same bytes. 1 <= n <= 8192. */
+int pc_sim_matrix(pc_ctx* ctx, const float* d_F, int n, int dim, float* d_S);
+/* mmr_select_with_q (dataset_curator.py:211-238) on the device: d_S [n][n] f32 symmetric, d_q [n] f32,
+ * d_order [k] i32; score = alpha q - (1 - alpha) max(0, max over picked S) in f64, greatest first,
+ * lowest index on ties. 1 <= k <= n <= 8192. */
+int pc_mmr_order(pc_ctx* ctx, const float* d_S, const float* d_q, int n, int k, double alpha, int32_t* d_order);
 
 /* ---- host-side align geometry (CPU, batched) ---- */
 /* cv::estimateAffinePartial2D(from, to, method=LMEDS) for n point sets of npts points each

@@ -72,6 +72,16 @@ class CropDesc(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class CurateDesc(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("row_stride", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("w2", C.c_int32), ("h2", C.c_int32), ("kind", C.c_int32 * 2), ("isx", C.c_int32 * 2),
+                ("isy", C.c_int32 * 2), ("xs", C.c_int32 * 2), ("ys", C.c_int32 * 2), ("pad_", C.c_int32)]
+
+
+PC_CURATE_COPY, PC_CURATE_FAST, PC_CURATE_AREA = 0, 1, 2
+CURATE_RECORD_BYTES = 1312   # sizeof(pc_curate_record)
+
+assert C.sizeof(CurateDesc) == 72
 assert C.sizeof(YoloLetterboxDesc) == 64 and C.sizeof(YoloScale) == 20 and C.sizeof(CropDesc) == 24
 assert C.sizeof(ResizeDesc) == 80 and C.sizeof(LetterboxDesc) == 56 and C.sizeof(WarpDesc) == 96 and C.sizeof(AreaTab) == 12
 
@@ -150,6 +160,10 @@ SIGNATURES = {
     "pc_l2_normalize": ([_P, _P, _I, _I, _I, _F, _P], _I),
     "pc_pil_bicubic_coeffs": ([_I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I], _I),
     "pc_clip_geometry": ([_I, _I, _I, C.POINTER(C.c_int32)], _I),
+    "pc_crop_metrics_layout": ([C.POINTER(CurateDesc), _I, C.POINTER(C.c_uint64), C.POINTER(_SZ), C.POINTER(_SZ)], _I),
+    "pc_crop_metrics": ([_P, C.POINTER(CurateDesc), _I, _P, _I, _P, _I, _P, _P, _SZ, _P, _SZ], _I),
+    "pc_sim_matrix": ([_P, _P, _I, _I, _P], _I),
+    "pc_mmr_order": ([_P, _P, _P, _I, _I, C.c_double, _P], _I),
 }
 
 

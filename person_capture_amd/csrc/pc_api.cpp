@@ -24,6 +24,7 @@
 #include <system_error>
 #include "../../include/pcgpu.h"
 #include "pc_common.h"
+#include "pc_curate.h"
 
 namespace pc {
 hipError_t conv_launch(int f32, int rowb, int cfg, const ConvParams& p, hipStream_t s);
@@ -80,6 +81,10 @@ hipError_t resize_area_launch(const uint8_t* src, int row_stride, const AreaTab*
 hipError_t resize_area_rows_launch(const void* jobs, int n, int row_stride, const AreaTab* xtab, const int* xstart,
                                   const AreaTab* ytab, const int* ystart, int OH, int OW, int span_bytes,
                                   hipStream_t s);
+hipError_t curate_metrics_launch(const void* d_imgs, int n, const void* d_bands, int nbands, const void* d_tabs,
+                                 const int* d_starts, const double* d_dct, int max_pixels, hipStream_t s);
+hipError_t sim_matrix_launch(const float* F, int n, int dim, float* S, hipStream_t s);
+hipError_t mmr_order_launch(const float* S, const float* q, int n, int k, double alpha, int* order, hipStream_t s);
 hipError_t embed_finalize_launch(const float* e, int ld, int n, int dim, int flip, float* out, hipStream_t s);
 hipError_t bank_match_launch(const float* q, int n, const float* bank, int B, int dim, float* fd, int* idx,
                              hipStream_t s);
@@ -148,6 +153,7 @@ using namespace pc;
 static_assert(sizeof(pc_letterbox_desc) == 56, "letterbox desc layout");
 static_assert(sizeof(pc_warp_desc) == 96, "warp desc layout");
 static_assert(sizeof(pc_area_tab) == 12, "area tab layout");
+static_assert(sizeof(pc_curate_desc) == 72 && sizeof(pc_curate_record) == 1312, "curate layouts");
 static_assert(sizeof(pc_resize_desc) == 80, "resize desc layout");
 static_assert(sizeof(pc_yolo_letterbox_desc) == 64, "yolo letterbox desc layout");
 static_assert(sizeof(pc_yolo_scale) == 20, "yolo scale layout");
@@ -2768,5 +2774,111 @@ extern "C" int pc_l2_normalize(pc_ctx* c, const float* e, int ld, int n, int dim
   if (!c || n < 0 || !e || !out) return fail(c, PC_ERR_ARG, "pc_l2_normalize: bad arguments");
   if (n == 0) return PC_OK;
   HIPCHK(c, embed_l2_launch(e, ld, n, dim, eps, out, c->stream));
+  return PC_OK;
+}
+
+// ---- dataset curator ----
+// A target's tables, checked on the host before anything is launched: monotone starts inside the
+// coefficient array, every source index inside the gray plane's axis.
+static bool curate_tables_ok(const pc_area_tab* tabs, int n_tabs, const int32_t* starts, int n_starts, int at, int dlen,
+                             int slen) {
+  if (at < 0 || (long long)at + dlen + 1 > n_starts) return false;
+  const int32_t* s = starts + at;
+  if (s[0] < 0 || s[dlen] > n_tabs) return false;
+  for (int d = 0; d < dlen; ++d)
+    if (s[d + 1] < s[d]) return false;
+  for (int k = s[0]; k < s[dlen]; ++k)
+    if (tabs[k].si < 0 || tabs[k].si >= slen) return false;
+  return true;
+}
+
+extern "C" int pc_crop_metrics(pc_ctx* c, const pc_curate_desc* h, int n, const pc_area_tab* tabs, int n_tabs,
+                               const int32_t* starts, int n_starts, const double* h_dct, void* d_scratch,
+                               size_t scratch_bytes, void* d_out, size_t out_bytes) {
+  // (n <= 16384: the resize launch has two grid rows per image)
+  if (!c || n < 0 || n > 16384 || n_tabs < 0 || n_starts < 0) return fail(c, PC_ERR_ARG, "pc_crop_metrics: bad arguments");
+  if (n == 0) return PC_OK;
+  if (!h || !h_dct || !d_scratch || !d_out || (n_tabs > 0 && !tabs) || (n_starts > 0 && !starts))
+    return fail(c, PC_ERR_ARG, "pc_crop_metrics: null argument");
+  if (((uintptr_t)d_scratch & 15) || ((uintptr_t)d_out & 15))
+    return fail(c, PC_ERR_ARG, "pc_crop_metrics: buffers must be 16-byte aligned");
+  std::vector<uint64_t> off((size_t)n * 5);
+  size_t need_s = 0, need_o = 0;
+  if (pc_crop_metrics_layout(h, n, off.data(), &need_s, &need_o) != PC_OK)
+    return fail(c, PC_ERR_ARG, "pc_crop_metrics: bad image descriptor (32 <= w, h <= 16384, row_stride >= 3 w, "
+                               "w2 / h2 / kinds as sharpness_norm and phash64 resize)");
+  if (scratch_bytes < need_s || out_bytes < need_o)
+    return fail(c, PC_ERR_ARG, "pc_crop_metrics: scratch / output buffer smaller than pc_crop_metrics_layout asks");
+  std::vector<CurateImg> imgs((size_t)n);
+  std::vector<int> bands;
+  int max_pixels = 32 * 32;
+  for (int i = 0; i < n; ++i) {
+    const pc_curate_desc& q = h[i];
+    if (!q.d_src) return fail(c, PC_ERR_ARG, "pc_crop_metrics: null image");
+    const uint64_t* o = &off[(size_t)i * 5];
+    CurateImg& m = imgs[i];
+    m.src = q.d_src;
+    m.row_stride = q.row_stride; m.w = q.w; m.h = q.h;
+    m.gpitch = (q.w + 15) & ~15;
+    m.gray = (uint8_t*)d_scratch + o[0];
+    for (int t = 0; t < 2; ++t) {
+      CurateTarget& T = m.t[t];
+      T.ow = t ? 32 : q.w2;
+      T.oh = t ? 32 : q.h2;
+      T.kind = q.kind[t]; T.isx = q.isx[t]; T.isy = q.isy[t]; T.xs = q.xs[t]; T.ys = q.ys[t];
+      T.dst = (uint8_t*)d_scratch + o[1 + t];
+      T.pitch = T.kind == PC_CURATE_COPY ? m.gpitch : ((T.ow + 15) & ~15);
+      if (T.kind == PC_CURATE_AREA && (!curate_tables_ok(tabs, n_tabs, starts, n_starts, T.xs, T.ow, q.w) ||
+                                       !curate_tables_ok(tabs, n_tabs, starts, n_starts, T.ys, T.oh, q.h)))
+        return fail(c, PC_ERR_ARG, "pc_crop_metrics: INTER_AREA tables out of range");
+      max_pixels = std::max(max_pixels, T.ow * T.oh);
+    }
+    pc_curate_record* rec = (pc_curate_record*)((char*)d_out + o[3]);
+    m.sums = (unsigned long long*)&rec->sum_g2;
+    m.wh = &rec->w2;
+    m.hist = rec->hist;
+    m.coef = rec->coef;
+    m.row_sum = (unsigned*)((char*)d_out + o[4]);
+    m.col_sum = m.row_sum + q.h;
+    for (int y = 0; y < q.h; y += CURATE_BAND) { bands.push_back(i); bands.push_back(y); }
+  }
+  // one staged blob (a second stage_copy could wrap the ring over the first): descriptors, bands,
+  // coefficient table, starts, cosine table, each from a 16-byte boundary
+  auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+  const size_t o_img = 0, o_band = up16(o_img + imgs.size() * sizeof(CurateImg));
+  const size_t o_tab = up16(o_band + bands.size() * sizeof(int));
+  const size_t o_st = up16(o_tab + (size_t)n_tabs * sizeof(pc_area_tab));
+  const size_t o_dct = up16(o_st + (size_t)n_starts * sizeof(int32_t));
+  const size_t total = o_dct + 256 * sizeof(double);
+  std::vector<char> blob(total, 0);
+  memcpy(blob.data() + o_img, imgs.data(), imgs.size() * sizeof(CurateImg));
+  memcpy(blob.data() + o_band, bands.data(), bands.size() * sizeof(int));
+  if (n_tabs) memcpy(blob.data() + o_tab, tabs, (size_t)n_tabs * sizeof(pc_area_tab));
+  if (n_starts) memcpy(blob.data() + o_st, starts, (size_t)n_starts * sizeof(int32_t));
+  memcpy(blob.data() + o_dct, h_dct, 256 * sizeof(double));
+  void* dv = nullptr;
+  int rc = stage_copy(c, blob.data(), total, &dv);
+  if (rc) return rc;
+  char* db = (char*)dv;
+  HIPCHK(c, hipMemsetAsync(d_out, 0, need_o, c->stream));
+  HIPCHK(c, curate_metrics_launch(db + o_img, n, db + o_band, (int)(bands.size() / 2), db + o_tab,
+                                  (const int*)(db + o_st), (const double*)(db + o_dct), max_pixels, c->stream));
+  return PC_OK;
+}
+
+extern "C" int pc_sim_matrix(pc_ctx* c, const float* F, int n, int dim, float* S) {
+  if (!c || n < 0 || n > 8192 || dim <= 0) return fail(c, PC_ERR_ARG, "pc_sim_matrix: 0 <= n <= 8192, dim >= 1");
+  if (n == 0) return PC_OK;
+  if (!F || !S) return fail(c, PC_ERR_ARG, "pc_sim_matrix: null argument");
+  HIPCHK(c, sim_matrix_launch(F, n, dim, S, c->stream));
+  return PC_OK;
+}
+
+extern "C" int pc_mmr_order(pc_ctx* c, const float* S, const float* q, int n, int k, double alpha, int32_t* order) {
+  if (!c || n < 0 || n > 8192 || k < 0 || k > n || !(alpha == alpha))
+    return fail(c, PC_ERR_ARG, "pc_mmr_order: 0 <= k <= n <= 8192");
+  if (n == 0 || k == 0) return PC_OK;
+  if (!S || !q || !order) return fail(c, PC_ERR_ARG, "pc_mmr_order: null argument");
+  HIPCHK(c, mmr_order_launch(S, q, n, k, alpha, order, c->stream));
   return PC_OK;
 }

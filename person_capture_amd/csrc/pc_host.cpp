@@ -232,3 +232,59 @@ extern "C" int pc_clip_geometry(int h, int w, int side, int32_t* h_out4 /* rw, r
   h_out4[3] = (int)nearbyint((rw - side) / 2.0);
   return PC_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Buffer layout and argument checks of pc_crop_metrics (host only: no context, no device).
+// ---------------------------------------------------------------------------
+static bool curate_target_ok(int kind, int isx, int isy, int xs, int ys, int sw, int sh, int ow, int oh) {
+  if (ow < 1 || oh < 1 || ow > sw || oh > sh) return false;
+  if (kind == PC_CURATE_COPY) return ow == sw && oh == sh;
+  if (kind == PC_CURATE_FAST)
+    return isx >= 1 && isy >= 1 && (long long)ow * isx <= sw && (long long)oh * isy <= sh;
+  if (kind == PC_CURATE_AREA) return xs >= 0 && ys >= 0;
+  return false;
+}
+
+extern "C" int pc_crop_metrics_layout(const pc_curate_desc* d, int n, uint64_t* off, size_t* scratch_bytes,
+                                      size_t* out_bytes) {
+  if (n < 0 || (n > 0 && (!d || !off)) || !scratch_bytes || !out_bytes) return PC_ERR_ARG;
+  uint64_t so = 0;
+  uint64_t oo = ((uint64_t)n * sizeof(pc_curate_record) + 15) & ~uint64_t(15);
+  for (int i = 0; i < n; ++i) {
+    const pc_curate_desc& q = d[i];
+    if (q.w < 32 || q.h < 32 || q.w > 16384 || q.h > 16384 || (long long)q.row_stride < 3LL * q.w) return PC_ERR_ARG;
+    const int m = std::max(q.w, q.h);
+    int w2 = q.w, h2 = q.h;
+    if (m > 256) {
+      // sharpness_norm's int(round(w * s)): Python rounds the double product half to even, as nearbyint does
+      const double s = 256.0 / (double)m;
+      w2 = (int)nearbyint((double)q.w * s);
+      h2 = (int)nearbyint((double)q.h * s);
+    }
+    if (q.w2 != w2 || q.h2 != h2) return PC_ERR_ARG;   // (w2 or h2 == 0: cv2.resize raises there too)
+    if (!curate_target_ok(q.kind[0], q.isx[0], q.isy[0], q.xs[0], q.ys[0], q.w, q.h, w2, h2)) return PC_ERR_ARG;
+    if (!curate_target_ok(q.kind[1], q.isx[1], q.isy[1], q.xs[1], q.ys[1], q.w, q.h, 32, 32)) return PC_ERR_ARG;
+    const uint64_t gpitch = ((uint64_t)q.w + 15) & ~uint64_t(15);
+    uint64_t* o = off + (size_t)i * 5;
+    o[0] = so;
+    so += gpitch * (uint64_t)q.h;
+    if (q.kind[0] == PC_CURATE_COPY) {
+      o[1] = o[0];
+    } else {
+      o[1] = so;
+      so += (((uint64_t)w2 + 15) & ~uint64_t(15)) * (uint64_t)h2;
+    }
+    if (q.kind[1] == PC_CURATE_COPY) {
+      o[2] = o[0];
+    } else {
+      o[2] = so;
+      so += 32 * 32;
+    }
+    o[3] = (uint64_t)i * sizeof(pc_curate_record);
+    o[4] = oo;
+    oo += (((uint64_t)q.h + (uint64_t)q.w) * 4 + 15) & ~uint64_t(15);
+  }
+  *scratch_bytes = (size_t)so;
+  *out_bytes = (size_t)oo;
+  return PC_OK;
+}

@@ -20,6 +20,8 @@
 
 #pragma clang fp contract(off)
 
+#include "pc_area.h"
+
 namespace pc {
 
 // ---------------------------------------------------------------------------
@@ -375,8 +377,7 @@ __global__ void rotate_pad_u8(const uint8_t* __restrict__ src, int H, int W, int
 // Coefficient tables (xofs: src index, dst index, weight) are built on the host
 // exactly as cv::computeResizeAreaTab does and passed in.
 // ---------------------------------------------------------------------------
-struct AreaTab { int si; int di; float alpha; };
-
+// (AreaTab and the per-pixel arithmetic: pc_area.h, shared with the one-channel kernel of pc_curate.hip)
 __global__ void resize_area_u8(const uint8_t* __restrict__ src, int row_stride,
                                const AreaTab* __restrict__ xtab, const int* __restrict__ xtab_start,
                                const AreaTab* __restrict__ ytab, const int* __restrict__ ytab_start,
@@ -384,25 +385,8 @@ __global__ void resize_area_u8(const uint8_t* __restrict__ src, int row_stride,
   const int pix = blockIdx.x * blockDim.x + threadIdx.x;
   if (pix >= OH * OW) return;
   const int dy = pix / OW, dx = pix - (pix / OW) * OW;
-  float acc[3] = {0.f, 0.f, 0.f};
-  for (int j = ytab_start[dy]; j < ytab_start[dy + 1]; ++j) {
-    const AreaTab ty = ytab[j];
-    const uint8_t* row = src + (long long)ty.si * row_stride;
-    float rs[3] = {0.f, 0.f, 0.f};
-    for (int i = xtab_start[dx]; i < xtab_start[dx + 1]; ++i) {
-      const AreaTab tx = xtab[i];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rs[c] += (float)row[tx.si * 3 + c] * tx.alpha;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += rs[c] * ty.alpha;
-  }
-  uint8_t* o = dst + (long long)pix * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    int v = __float2int_rn(acc[c]);
-    o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-  }
+  area_pixel<3>(src, row_stride, xtab, xtab_start[dx], xtab_start[dx + 1], ytab, ytab_start[dy], ytab_start[dy + 1],
+                dst + (long long)pix * 3);
 }
 
 // The same arithmetic for a batch of equally sized frames (the pre-scan's 4K -> 416 downscale of a
@@ -543,18 +527,7 @@ __global__ void resize_area_fast_u8(const uint8_t* __restrict__ src, int row_str
   const int pix = blockIdx.x * blockDim.x + threadIdx.x;
   if (pix >= OH * OW) return;
   const int dy = pix / OW, dx = pix - (pix / OW) * OW;
-  const float scale = 1.f / (float)(isx * isy);
-  uint8_t* o = dst + (long long)pix * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    int sum = 0;
-    for (int j = 0; j < isy; ++j) {
-      const uint8_t* row = src + (long long)(dy * isy + j) * row_stride + (dx * isx) * 3 + c;
-      for (int i = 0; i < isx; ++i) sum += row[i * 3];
-    }
-    int v = (isx == 2 && isy == 2) ? ((sum + 2) >> 2) : __float2int_rn((float)sum * scale);
-    o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-  }
+  area_fast_pixel<3>(src, row_stride, isx, isy, dx, dy, dst + (long long)pix * 3);
 }
 
 // ---------------------------------------------------------------------------

@@ -42,6 +42,50 @@ def _clamp(v, lo, hi):
     return max(lo, min(hi, v))
 
 
+def black_border_roi(row_sum, col_sum, thr=10, max_scan=None):
+    """The scan of detect_black_borders (utils.py:162-196) on the gray plane's row and column sums:
+    a row of W pixels has `mean > thr` exactly when `sum > thr * W` (integer sums; the f64 quotient
+    cannot round across an integer threshold at W <= 16384)."""
+    H, W = len(row_sum), len(col_sum)
+    if max_scan is None:
+        max_scan = max(64, min(H, W) // 8)
+    top = 0
+    for r in range(min(H, max_scan)):
+        if int(row_sum[r]) > thr * W:
+            break
+        top = r + 1
+    bottom = H
+    for r in range(H - 1, max(H - max_scan - 1, -1), -1):
+        if int(row_sum[r]) > thr * W:
+            break
+        bottom = r
+    left = 0
+    for c in range(min(W, max_scan)):
+        if int(col_sum[c]) > thr * H:
+            break
+        left = c + 1
+    right = W
+    for c in range(W - 1, max(W - max_scan - 1, -1), -1):
+        if int(col_sum[c]) > thr * H:
+            break
+        right = c
+    left = _clamp(left, 0, right - 1)
+    top = _clamp(top, 0, bottom - 1)
+    right = _clamp(right, left + 1, W)
+    bottom = _clamp(bottom, top + 1, H)
+    return int(left), int(top), int(right), int(bottom)
+
+
+def detect_black_borders(bgr, thr=10, max_scan=None):
+    """utils.py:152-196: ROI (x1, y1, x2, y2) inside constant black borders. The gray plane's row and
+    column sums come from curate.crop_metrics_batch (the device with a default context, else NumPy)."""
+    if bgr is None or bgr.size == 0:
+        return (0, 0, 0, 0)
+    from . import curate
+    m = curate.crop_metrics_batch([bgr])[0]
+    return black_border_roi(m.row_sum, m.col_sum, thr, max_scan)
+
+
 def expand_box_to_ratio(x1, y1, x2, y2, ratio_w, ratio_h, frame_w, frame_h, anchor=None, head_bias=0.0):
     """utils.py:198-257: the smallest box of exactly ratio_w:ratio_h around the input box
     (optionally re-centred on `anchor` and shifted by head_bias * box height), clamped into
