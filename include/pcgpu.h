@@ -33,6 +33,9 @@
  *   pc_resize_area_batch               the same over a chunk of pre-scan samples (gui_app.py:1505-1507)
  *   pc_resize_linear                   cv2.resize(..., INTER_LINEAR) (face_embedder.py:2264, 2460)
  *   pc_resize_area_fast                cv2.resize(..., INTER_AREA) at integer ratios (face_embedder.py:2460)
+ *   pc_face_chips                      the unaligned face chips of the OpenCLIP face mode: cv2.resize(face_bgr,
+ *                                      (112,112), INTER_AREA if max(h,w) > 112 else INTER_LINEAR) per kept face
+ *                                      (face_embedder.py:2454-2460, 2132-2141), all faces of a batch at once
  *   pc_yolo_detect                     PersonDetector.detect -> [ext] ultralytics YOLO.predict(conf, iou=0.45,
  *                                      classes=[0], max_det=40, imgsz=640) (detectors.py:271-296)
  *   pc_yolo_pose_detect                FaceEmbedder YOLOv8-face backend (Y8F_DEFAULT, face_embedder.py:33) ->
@@ -151,6 +154,20 @@ typedef struct pc_crop_desc {
   const uint8_t* d_src;
   int32_t H, W, row_stride, pad_;
 } pc_crop_desc;
+
+/* One face rectangle of pc_face_chips: BGR u8 on the device (top-left pointer at any byte offset of a
+ * frame, size, bytes per row of the frame). */
+typedef struct pc_chip_desc {
+  const uint8_t* d_src;
+  int32_t H, W, row_stride, pad_;
+} pc_chip_desc;
+/* the cv::resize path of a rectangle (pc_face_chip_plan) */
+#define PC_CHIP_COPY 0      /* 112 x 112: copied */
+#define PC_CHIP_AREA_FAST 1 /* INTER_AREA at integer ratios (1 on an axis included) */
+#define PC_CHIP_AREA 2      /* INTER_AREA, both axes shrink: generic float coefficients */
+#define PC_CHIP_LINEAR 3    /* bilinear; area_mode 1 when INTER_AREA was asked but an axis upscales */
+#define PC_CHIP_SIDE 112
+#define PC_CHIP_MAX_SIDE 16384
 
 /* One crop of the dataset curator's metrics batch (pc_crop_metrics): a BGR u8 image on the device and
  * the geometry of its two INTER_AREA targets, [0] the <= 256 plane of sharpness_norm (w2 x h2;
@@ -305,6 +322,18 @@ int pc_resize_area(pc_ctx* ctx, const uint8_t* d_src, int row_stride, const pc_a
 int pc_resize_area_batch(pc_ctx* ctx, const uint8_t* const* h_srcs, uint8_t* const* h_dsts, int n, int row_stride,
                          const pc_area_tab* h_xtab, const int32_t* h_xstart, int n_x, const pc_area_tab* h_ytab,
                          const int32_t* h_ystart, int n_y, int OH, int OW);
+/* Host only (no context, no device): which path OpenCV 4.9's cv::resize takes for an H x W u8 rectangle
+ * resized to 112 x 112 with INTER_AREA if max(H, W) > 112 else INTER_LINEAR, as pc_face_chips decides it
+ * (the same decision as imageops.resize_plan). h_out4 = PC_CHIP_* kind, isx, isy (integer ratios, for
+ * PC_CHIP_AREA_FAST), area_mode (for PC_CHIP_LINEAR). PC_ERR_ARG unless 1 <= H, W <= PC_CHIP_MAX_SIDE. */
+int pc_face_chip_plan(int H, int W, int32_t* h_out4);
+/* n face rectangles of any sizes and paths -> d_chips [n][112][112][3] u8, chip i exactly
+ * cv2.resize(rectangle i, (112,112), INTER_AREA if max(H,W) > 112 else INTER_LINEAR): the bytes of
+ * pc_copy_2d / pc_resize_area_fast / pc_resize_area / pc_resize_linear for that rectangle. One descriptor
+ * upload and one launch whatever n and the mix of sizes; the INTER_AREA coefficients are derived on the
+ * device. n == 0: PC_OK, nothing enqueued. A null pointer, H or W outside [1, PC_CHIP_MAX_SIDE],
+ * row_stride < 3 W or n < 0: PC_ERR_ARG before anything is enqueued. */
+int pc_face_chips(pc_ctx* ctx, const pc_chip_desc* h_descs, int n, uint8_t* d_chips);
 
 /* ---- detection ---- */
 /* Runs letterbox -> SCRFD net -> decode(score >= det_thresh) -> NMS(nms_thresh) for n frames.

@@ -72,6 +72,16 @@ class CropDesc(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class ChipDesc(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("row_stride", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+PC_CHIP_COPY, PC_CHIP_AREA_FAST, PC_CHIP_AREA, PC_CHIP_LINEAR = 0, 1, 2, 3
+CHIP_KINDS = {PC_CHIP_COPY: "copy", PC_CHIP_AREA_FAST: "area_fast", PC_CHIP_AREA: "area", PC_CHIP_LINEAR: "linear"}
+CHIP_BYTES = 112 * 112 * 3
+
+
 class CurateDesc(C.Structure):
     _fields_ = [("d_src", C.c_void_p), ("row_stride", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
                 ("w2", C.c_int32), ("h2", C.c_int32), ("kind", C.c_int32 * 2), ("isx", C.c_int32 * 2),
@@ -81,7 +91,7 @@ class CurateDesc(C.Structure):
 PC_CURATE_COPY, PC_CURATE_FAST, PC_CURATE_AREA = 0, 1, 2
 CURATE_RECORD_BYTES = 1312   # sizeof(pc_curate_record)
 
-assert C.sizeof(CurateDesc) == 72
+assert C.sizeof(CurateDesc) == 72 and C.sizeof(ChipDesc) == 24
 assert C.sizeof(YoloLetterboxDesc) == 64 and C.sizeof(YoloScale) == 20 and C.sizeof(CropDesc) == 24
 assert C.sizeof(ResizeDesc) == 80 and C.sizeof(LetterboxDesc) == 56 and C.sizeof(WarpDesc) == 96 and C.sizeof(AreaTab) == 12
 
@@ -143,6 +153,8 @@ SIGNATURES = {
                         C.POINTER(C.c_int32), _I, _P, _I, _I], _I),
     "pc_resize_area_batch": ([_P, _P, _P, _I, _I, C.POINTER(AreaTab), C.POINTER(C.c_int32), _I, C.POINTER(AreaTab),
                               C.POINTER(C.c_int32), _I, _I, _I], _I),
+    "pc_face_chip_plan": ([_I, _I, C.POINTER(C.c_int32)], _I),
+    "pc_face_chips": ([_P, C.POINTER(ChipDesc), _I, _P], _I),
     "pc_scrfd_detect": ([_P, C.POINTER(LetterboxDesc), _I, _I, _F, _F, C.POINTER(_F), _I, _P, _P, _P, _P], _I),
     "pc_embed_finalize": ([_P, _P, _I, _I, _I, _I, _P], _I),
     "pc_arcface_embed": ([_P, _P, _I, _I, _P], _I),

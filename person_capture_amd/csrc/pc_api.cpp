@@ -40,6 +40,7 @@ hipError_t resize_area_launch(const uint8_t* src, int row_stride, const AreaTab*
 hipError_t resize_area_rows_launch(const void* jobs, int n, int row_stride, const AreaTab* xtab, const int* xstart,
                                   const AreaTab* ytab, const int* ystart, int OH, int OW, int span_bytes,
                                   hipStream_t s);
+hipError_t face_chips_launch(const void* d_jobs, int n, hipStream_t s);
 hipError_t curate_metrics_launch(const void* d_imgs, int n, const void* d_bands, int nbands, const void* d_tabs,
                                  const int* d_starts, const double* d_dct, int max_pixels, hipStream_t s);
 hipError_t sim_matrix_launch(const float* F, int n, int dim, float* S, hipStream_t s);
@@ -103,6 +104,7 @@ static_assert(sizeof(pc_warp_desc) == 96, "warp desc layout");
 static_assert(sizeof(pc_area_tab) == 12, "area tab layout");
 static_assert(sizeof(pc_curate_desc) == 72 && sizeof(pc_curate_record) == 1312, "curate layouts");
 static_assert(sizeof(pc_resize_desc) == 80, "resize desc layout");
+static_assert(sizeof(pc_chip_desc) == 24, "chip desc layout");
 static_assert(sizeof(pc_yolo_letterbox_desc) == 64, "yolo letterbox desc layout");
 static_assert(sizeof(pc_yolo_scale) == 20, "yolo scale layout");
 
@@ -591,6 +593,81 @@ extern "C" int pc_resize_area_fast(pc_ctx* c, const uint8_t* src, int row_stride
   return PC_OK;
 }
 
+// ---- face chips of the OpenCLIP face mode ----
+// cv::resize's dispatch (OpenCV 4.9 imgproc/src/resize.cpp: cv::resize then hal::resize) for H x W -> 112 x 112,
+// INTER_AREA if max(H, W) > 112 else INTER_LINEAR; imageops.resize_plan states the same for any target.
+struct ChipPlan { int kind, isx, isy, area_mode; double inv_x, inv_y, scale_x, scale_y; };
+
+static ChipPlan chip_plan(int H, int W) {
+  ChipPlan p{};
+  p.inv_x = (double)PC_CHIP_SIDE / W;
+  p.inv_y = (double)PC_CHIP_SIDE / H;
+  p.scale_x = 1.0 / p.inv_x;   // (not W / 112: they can differ in the last bit)
+  p.scale_y = 1.0 / p.inv_y;
+  p.isx = (int)std::nearbyint(p.scale_x);   // cvRound
+  p.isy = (int)std::nearbyint(p.scale_y);
+  if (H == PC_CHIP_SIDE && W == PC_CHIP_SIDE) { p.kind = PC_CHIP_COPY; return p; }
+  bool area = std::max(H, W) > PC_CHIP_SIDE;
+  const double eps = 2.220446049250313e-16;
+  const bool fast = std::fabs(p.scale_x - p.isx) < eps && std::fabs(p.scale_y - p.isy) < eps &&
+                    W == p.isx * PC_CHIP_SIDE && H == p.isy * PC_CHIP_SIDE;
+  if (!area && fast && p.isx == 2 && p.isy == 2) area = true;   // (INTER_LINEAR at exactly 2 x 2 down)
+  if (area && p.scale_x >= 1 && p.scale_y >= 1) {
+    p.kind = fast ? PC_CHIP_AREA_FAST : PC_CHIP_AREA;
+  } else {
+    p.kind = PC_CHIP_LINEAR;
+    p.area_mode = area ? 1 : 0;
+  }
+  return p;
+}
+
+static bool chip_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= PC_CHIP_MAX_SIDE && W <= PC_CHIP_MAX_SIDE; }
+
+extern "C" int pc_face_chip_plan(int H, int W, int32_t* out4) {
+  if (!out4 || !chip_size_ok(H, W)) return PC_ERR_ARG;
+  const ChipPlan p = chip_plan(H, W);
+  out4[0] = p.kind; out4[1] = p.isx; out4[2] = p.isy; out4[3] = p.area_mode;
+  return PC_OK;
+}
+
+// OpenCV's 128-bit VResizeLinearVec_32s8u stops here in a row of 112 x 3 bytes (the 16-byte loop, then 8-byte
+// steps while x < width - 8; engines.opencv_vresize_simd_end)
+static int chip_simd_end() {
+  const int wb = PC_CHIP_SIDE * 3;
+  int x = wb / 16 * 16;
+  while (x < wb - 8) x += 8;
+  return x;
+}
+
+extern "C" int pc_face_chips(pc_ctx* c, const pc_chip_desc* h, int n, uint8_t* d_chips) {
+  if (!c) return PC_ERR_ARG;
+  if (n < 0 || (n > 0 && (!h || !d_chips))) return fail(c, PC_ERR_ARG, "pc_face_chips: bad arguments");
+  if (n == 0) return PC_OK;
+  struct Job { pc_resize_desc r; int32_t kind, isx, isy, pad_; };   // pc_image.hip ChipJob
+  static_assert(sizeof(Job) == 96, "chip job layout");
+  std::vector<Job> jobs((size_t)n);
+  const int simd_end = chip_simd_end();
+  for (int i = 0; i < n; ++i) {
+    const pc_chip_desc& d = h[i];
+    if (!d.d_src || !chip_size_ok(d.H, d.W) || (long long)d.row_stride < 3LL * d.W)
+      return fail(c, PC_ERR_ARG, "pc_face_chips: bad rectangle (non-null, 1 <= H, W <= 16384, row_stride >= 3 W)");
+    const ChipPlan p = chip_plan(d.H, d.W);
+    Job& j = jobs[i];
+    memset(&j, 0, sizeof(j));
+    j.r.d_src = d.d_src; j.r.H = d.H; j.r.W = d.W; j.r.row_stride = d.row_stride;
+    j.r.new_w = j.r.new_h = PC_CHIP_SIDE;
+    j.r.scale_x = p.scale_x; j.r.scale_y = p.scale_y; j.r.inv_x = p.inv_x; j.r.inv_y = p.inv_y;
+    j.r.simd_end = simd_end; j.r.area_mode = p.area_mode;
+    j.r.d_dst = d_chips + (size_t)i * PC_CHIP_SIDE * PC_CHIP_SIDE * 3;
+    j.kind = p.kind; j.isx = p.isx; j.isy = p.isy;
+  }
+  void* dj;
+  int rc = stage_copy(c, jobs.data(), sizeof(Job) * (size_t)n, &dj);
+  if (rc) return rc;
+  HIPCHK(c, face_chips_launch(dj, n, c->stream));
+  return PC_OK;
+}
+
 extern "C" int pc_embed_finalize(pc_ctx* c, const float* e, int ld, int n, int dim, int flip, float* out) {
   if (!c || n < 0) return fail(c, PC_ERR_ARG, "pc_embed_finalize: bad arguments");
   if (n == 0) return PC_OK;
@@ -861,17 +938,28 @@ static bool clip_geom_ok(int side, int patch) {
 extern "C" int pc_clip_prep_geom(pc_ctx* c, int prec, int side, int patch, const pc_crop_desc* h, int n, void* out) {
   if (!c || !h || n <= 0 || !out) return fail(c, PC_ERR_ARG, "pc_clip_prep: bad arguments");
   if (!clip_geom_ok(side, patch)) return fail(c, PC_ERR_ARG, "pc_clip_prep: side in {224, 336}, patch in {14, 16, 32}, side % patch == 0");
-  // host: geometry + Pillow coefficient tables for the `side` kept columns / rows of each crop
+  // host: geometry + Pillow coefficient tables for the `side` kept columns / rows of each crop size; crops
+  // of one size share one table (the 112 x 112 chips of the OpenCLIP face mode: one table per call)
   struct Tabs { int kh, kv, row0, nrows; std::vector<int32_t> hb, hk, vb, vk; };
-  std::vector<Tabs> T(n);
+  std::vector<Tabs> T;
+  std::map<std::pair<int, int>, int> tab_of_size;
+  std::vector<int> ti(n);
   size_t tmp_bytes = 0, tab_ints = 0;
   int max_rows = 0;
   for (int i = 0; i < n; ++i) {
     const pc_crop_desc& d = h[i];
     if (!d.d_src || d.H <= 0 || d.W <= 0 || d.row_stride < d.W * 3) return fail(c, PC_ERR_ARG, "pc_clip_prep: bad crop");
+    const auto seen = tab_of_size.find({d.H, d.W});
+    if (seen != tab_of_size.end()) {
+      ti[i] = seen->second;
+      tmp_bytes += (size_t)T[ti[i]].nrows * side * 3;
+      continue;
+    }
+    ti[i] = tab_of_size[{d.H, d.W}] = (int)T.size();
     int32_t g[4];
     pc_clip_geometry(d.H, d.W, side, g);
-    Tabs& t = T[i];
+    T.emplace_back();
+    Tabs& t = T.back();
     t.hb.resize(2 * side); t.vb.resize(2 * side);
     t.hk.resize((size_t)side * kClipKmax); t.vk.resize((size_t)side * kClipKmax);
     t.kh = pc_pil_bicubic_coeffs(d.W, g[0], g[3], side, t.hb.data(), t.hk.data(), kClipKmax);
@@ -893,8 +981,8 @@ extern "C" int pc_clip_prep_geom(pc_ctx* c, int prec, int side, int patch, const
   }
   std::vector<int32_t> tabs;
   tabs.reserve(tab_ints);
-  std::vector<size_t> off(n * 4);
-  for (int i = 0; i < n; ++i) {
+  std::vector<size_t> off(T.size() * 4);
+  for (int i = 0; i < (int)T.size(); ++i) {
     off[4 * i + 0] = tabs.size(); tabs.insert(tabs.end(), T[i].hb.begin(), T[i].hb.end());
     off[4 * i + 1] = tabs.size(); tabs.insert(tabs.end(), T[i].hk.begin(), T[i].hk.end());
     off[4 * i + 2] = tabs.size(); tabs.insert(tabs.end(), T[i].vb.begin(), T[i].vb.end());
@@ -908,12 +996,13 @@ extern "C" int pc_clip_prep_geom(pc_ctx* c, int prec, int side, int patch, const
   for (int i = 0; i < n; ++i) {
     ClipPrepDesc& d = descs[i];
     const int32_t* tb = (const int32_t*)dtab;
+    const int k = ti[i];
     d.src = h[i].d_src; d.H = h[i].H; d.W = h[i].W; d.row_stride = h[i].row_stride;
-    d.kh = T[i].kh; d.kv = T[i].kv;
-    d.hb = tb + off[4 * i]; d.hk = tb + off[4 * i + 1]; d.vb = tb + off[4 * i + 2]; d.vk = tb + off[4 * i + 3];
-    d.row0 = T[i].row0; d.nrows = T[i].nrows;
+    d.kh = T[k].kh; d.kv = T[k].kv;
+    d.hb = tb + off[4 * k]; d.hk = tb + off[4 * k + 1]; d.vb = tb + off[4 * k + 2]; d.vk = tb + off[4 * k + 3];
+    d.row0 = T[k].row0; d.nrows = T[k].nrows;
     d.tmp = (uint8_t*)c->clip_tmp + tmp_off;
-    tmp_off += (size_t)T[i].nrows * side * 3;
+    tmp_off += (size_t)T[k].nrows * side * 3;
   }
   void* ddesc;
   if ((rc = stage_copy(c, descs.data(), sizeof(ClipPrepDesc) * n, &ddesc))) return rc;

@@ -122,11 +122,8 @@ __device__ __forceinline__ void lin_coef_area(int d, double scale, double inv, i
   a1 = (short)__float2int_rn(f * 2048.f);
 }
 
-__global__ void resize_linear_u8(const ResizeDesc* __restrict__ descs) {
-  const ResizeDesc d = descs[blockIdx.y];
-  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pix >= d.new_w * d.new_h) return;
-  const int y = pix / d.new_w, x = pix - (pix / d.new_w) * d.new_w;
+// output pixel (x, y) of job d, written at o
+__device__ __forceinline__ void linear_pixel(const ResizeDesc& d, int x, int y, uint8_t* o) {
   int sx, sy;
   short a0, a1, b0, b1;
   if (d.area_mode) {
@@ -140,7 +137,6 @@ __global__ void resize_linear_u8(const ResizeDesc* __restrict__ descs) {
   const int sy1 = sy + 1 < d.H ? sy + 1 : sy;
   const uint8_t* r0 = d.src + (long long)sy * d.row_stride;
   const uint8_t* r1 = d.src + (long long)sy1 * d.row_stride;
-  uint8_t* o = d.dst + (long long)pix * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int S0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
@@ -153,6 +149,14 @@ __global__ void resize_linear_u8(const ResizeDesc* __restrict__ descs) {
     }
     o[c] = (uint8_t)(val < 0 ? 0 : (val > 255 ? 255 : val));
   }
+}
+
+__global__ void resize_linear_u8(const ResizeDesc* __restrict__ descs) {
+  const ResizeDesc d = descs[blockIdx.y];
+  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= d.new_w * d.new_h) return;
+  const int y = pix / d.new_w, x = pix - (pix / d.new_w) * d.new_w;
+  linear_pixel(d, x, y, d.dst + (long long)pix * 3);
 }
 
 // ---------------------------------------------------------------------------
@@ -528,6 +532,53 @@ __global__ void resize_area_fast_u8(const uint8_t* __restrict__ src, int row_str
   if (pix >= OH * OW) return;
   const int dy = pix / OW, dx = pix - (pix / OW) * OW;
   area_fast_pixel<3>(src, row_stride, isx, isy, dx, dy, dst + (long long)pix * 3);
+}
+
+// ---------------------------------------------------------------------------
+// Face chips of the OpenCLIP face mode (face_embedder.py:2454-2460, 2132-2141: no alignment, every kept
+// face is cv2.resize(face, (112, 112), INTER_AREA if max(h, w) > 112 else INTER_LINEAR)): n source
+// rectangles of any sizes -> n chips in one launch. The host (pc_face_chips) picks each rectangle's
+// cv::resize path as imageops.resize_plan states it; a workgroup is 256 consecutive pixels of one
+// chip (49 per chip, XCD-remapped as the warp's so a chip's source rows stay in one L2) and runs
+// that path's per-pixel arithmetic - the functions the per-face kernels above run, so the bytes are
+// theirs. The INTER_AREA coefficients are derived here per destination index (area_span), not
+// uploaded. Byte loads only: a rectangle starts at any byte of a frame, and no load leaves
+// [row, row + 3 W) of a source row.
+// ---------------------------------------------------------------------------
+enum { CHIP_COPY = 0, CHIP_AREA_FAST = 1, CHIP_AREA = 2, CHIP_LINEAR = 3 };
+constexpr int CHIP_SIDE = 112, CHIP_WGS = CHIP_SIDE * CHIP_SIDE / 256;   // 49 x 256 = 112 x 112 exactly
+struct ChipJob { ResizeDesc r; int kind, isx, isy, pad_; };
+
+__global__ __launch_bounds__(256) void face_chips_u8(const ChipJob* __restrict__ jobs, int nwg) {
+  const int tile = xcd_remap(blockIdx.x, nwg);
+  const int chip = tile / CHIP_WGS;
+  const ChipJob& j = jobs[chip];
+  const int pix = (tile - chip * CHIP_WGS) * 256 + threadIdx.x;
+  const int y = pix / CHIP_SIDE, x = pix - y * CHIP_SIDE;
+  const int kind = j.kind;
+  const uint8_t* src = j.r.src;
+  const int stride = j.r.row_stride;
+  uint8_t* o = j.r.dst + pix * 3;
+  if (kind == CHIP_LINEAR) {
+    const ResizeDesc d = j.r;
+    linear_pixel(d, x, y, o);
+  } else if (kind == CHIP_AREA) {
+    const AreaSpan sx = area_span(x, j.r.W, j.r.scale_x), sy = area_span(y, j.r.H, j.r.scale_y);
+    area_pixel_taps<3>(src, stride, [&](int i) { return area_span_tap(sx, x, i); }, 0, sx.n,
+                       [&](int i) { return area_span_tap(sy, y, i); }, 0, sy.n, o);
+  } else if (kind == CHIP_AREA_FAST) {
+    area_fast_pixel<3>(src, stride, j.isx, j.isy, x, y, o);
+  } else {
+    const uint8_t* s = src + (long long)y * stride + x * 3;
+    o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
+  }
+}
+
+hipError_t face_chips_launch(const void* d_jobs, int n, hipStream_t s) {
+  const long long nwg = (long long)n * CHIP_WGS;
+  if (nwg <= 0 || nwg >= (1LL << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(face_chips_u8, dim3((unsigned)nwg), dim3(256), 0, s, (const ChipJob*)d_jobs, (int)nwg);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

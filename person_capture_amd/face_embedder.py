@@ -28,10 +28,21 @@ network here) seeded synthetic weights of the same architectures stand in
 
 The YOLOv8-face backend (the reference default, Y8F_DEFAULT) runs too: face_yolo.py
 (YOLOv8 Pose program on the device, the branch policy of face_embedder.py:1671-2093 on the
-host, 0-degree predicts batched across frames in extract_batch). The OpenCLIP face-embedding
-backend (use_arcface=False) is not on this build's hot path and raises RuntimeError at
-construction, as the reference does for unavailable backends. Host frames reach the device
-through the native pinned staging ring (pc_frame_stage) on a copy stream.
+host, 0-degree predicts batched across frames in extract_batch).
+
+use_arcface=False (the curator without a reference image, dataset_curator.py:329-336, and the GUI's
+"use ArcFace" switch) embeds with an OpenCLIP image tower instead, on the SCRFD backend
+(face_embedder.py:955-965, 1649-1661, 2454-2465): no alignment, every kept face is resized to a
+112x112 chip, and the chip goes through open_clip's preprocess into the tower:
+
+  cv2.resize(face, (112,112), AREA / LINEAR) (CPU)  pc_face_chips (device, all faces of a batch in one launch)
+  PIL + open_clip preprocess + encode_image (fp32)  pc_clip_embed_geom: Pillow-exact resample + ViT tower + L2
+
+(clip_model_name picks the tower, models_clip.CLIP_CFGS; PERSON_CAPTURE_AMD_FACE_CLIP_PRECISION f32 /
+f16 / f16x3 and PERSON_CAPTURE_AMD_FACE_CLIP_BATCH its arithmetic and batch) With the
+YOLOv8-face backend use_arcface=False raises RuntimeError at construction, as the reference does for
+unavailable backends. Host frames reach the device through the native pinned staging ring
+(pc_frame_stage) on a copy stream.
 """
 from __future__ import annotations
 
@@ -43,10 +54,12 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import imageops, models, onnx_models
-from ._lib import PC_PREC_F16, PC_PREC_F16C8, PC_PREC_F16X3, PC_PREC_F32, ResizeDesc, WarpDesc, check
+from . import imageops, models, models_clip, onnx_models
+from ._lib import (CHIP_BYTES, PC_PREC_F16, PC_PREC_F16C8, PC_PREC_F16X3, PC_PREC_F32, ChipDesc, ResizeDesc, WarpDesc,
+                   check)
 from .engines import ArcFaceEngine, ScrfdEngine, opencv_vresize_simd_end
 from .face_yolo import YoloFaceBranch
+from .reid_embedder import ClipEngine, clip_weights
 from .runtime import GpuContext
 
 Y8F_DEFAULT = "yolov8l-face.pt"   # reference default (face_embedder.py:33)
@@ -155,6 +168,15 @@ def _arc_precision() -> int:
     return p
 
 
+def _clip_face_precision() -> int:
+    """Precision of the OpenCLIP face tower (use_arcface=False). Default f32: the reference runs
+    encode_image in fp32 (face_embedder.py:1657-1660). PERSON_CAPTURE_AMD_FACE_CLIP_PRECISION=f16 (cosine
+    >= 0.99 only) / f16x3 (f32 class on the f16 matrix cores, within 1e-4) select the
+    others, with the bounds reid_embedder.py documents for the same towers; anything else raises."""
+    p = _prec_word("PERSON_CAPTURE_AMD_FACE_CLIP_PRECISION", (PC_PREC_F32, PC_PREC_F16, PC_PREC_F16X3))
+    return PC_PREC_F32 if p is None else p
+
+
 def synthetic_weights(kind: str, seed: int = 0) -> models.Params:
     key = (kind, seed)
     p = _WEIGHT_CACHE.get(key)
@@ -240,7 +262,8 @@ def dev_resize_batch(ctx: GpuContext, imgs: Sequence[_DevImage], keys: Sequence[
 
 
 class FaceEmbedder(YoloFaceBranch):
-    """Face detection (SCRFD, or the YOLOv8-face default) + ArcFace identity embedding on the MI355X.
+    """Face detection (SCRFD, or the YOLOv8-face default) + ArcFace identity embedding (or, with
+    use_arcface=False on SCRFD, OpenCLIP image-tower embeddings of the unaligned chips) on the MI355X.
     Returns list of dicts: {'bbox': np.int32[x1,y1,x2,y2], 'feat': np.float32[D], 'quality': float}."""
 
     def __init__(self, ctx: str = 'cuda', yolo_model: str = Y8F_DEFAULT, conf: float = 0.30,
@@ -255,18 +278,24 @@ class FaceEmbedder(YoloFaceBranch):
         override = os.getenv("PERSON_CAPTURE_AMD_FACE_MODEL", "").strip()
         if not model.lower().startswith("scrfd") and override:
             model = override
-        if not use_arcface:
-            raise RuntimeError("OpenCLIP face embeddings are not part of this MI355X build; use_arcface=True.")
         # backend choice as the reference (face_embedder.py:383-420, 500-520): names starting with
         # "scrfd" select SCRFD, anything else is a YOLOv8-face checkpoint name
         self.detector_backend = "scrfd" if os.path.basename(model).lower().startswith("scrfd") else "yolo"
+        if not use_arcface and self.detector_backend != "scrfd":
+            raise RuntimeError("use_arcface=False (OpenCLIP face embeddings) with the YOLOv8-face backend "
+                               f"({model or Y8F_DEFAULT}) is not part of this MI355X build; use an scrfd_* detector "
+                               "or use_arcface=True.")
         base = os.path.basename(model).lower().replace(".onnx", "").replace("_trt", "")
         self.scrfd_variant = "2.5g" if "2.5g" in base else "10g"
         self._scrfd_model_path = model
         self._device_index = _device_index(ctx)
         self.device = 'cuda'
-        self.use_arcface = True
-        self.backend = 'arcface'
+        self.use_arcface = bool(use_arcface)
+        self.backend = 'arcface' if self.use_arcface else 'clip'   # (face_embedder.py:929, 964)
+        self.clip_model_name, self.clip_pretrained = clip_model_name, clip_pretrained
+        if not self.use_arcface:
+            models_clip.clip_cfg(clip_model_name)   # RuntimeError for towers this build does not have
+            self.clip_precision = _clip_face_precision()
         self.det = None
         self.insight_app = None
         self.precision = _precision()
@@ -287,9 +316,13 @@ class FaceEmbedder(YoloFaceBranch):
         scrfd_file = model if model.lower().endswith(".onnx") else model + ".onnx"
         scrfd_path = onnx_models.find_model_file(scrfd_file) if self.detector_backend == "scrfd" else None
         arc_path = next((p for p in map(onnx_models.find_model_file,
-                                        (onnx_models.ARCFACE_ONNX,) + onnx_models.ARCFACE_ALT) if p), None)
+                                        (onnx_models.ARCFACE_ONNX,) + onnx_models.ARCFACE_ALT) if p), None) \
+            if self.use_arcface else None
         if os.getenv("PERSON_CAPTURE_AMD_REQUIRE_WEIGHTS", "0") == "1" and not (
                 (scrfd_path or self.detector_backend != "scrfd") and arc_path):
+            if not self.use_arcface:
+                raise RuntimeError(f"no OpenCLIP checkpoint ({clip_model_name} {clip_pretrained}) can be loaded "
+                                   "on this build: the face tower's weights are synthetic")
             raise RuntimeError(f"model files not found: {scrfd_file if not scrfd_path else ''} "
                                f"{onnx_models.ARCFACE_ONNX if not arc_path else ''}".strip())
         try:
@@ -302,7 +335,15 @@ class FaceEmbedder(YoloFaceBranch):
             else:
                 self._scrfd_params = synthetic_weights(f"scrfd_{self.scrfd_variant}", seed)
                 self.weights_source["scrfd"] = f"synthetic:scrfd_{self.scrfd_variant}:seed{seed}"
-            if arc_path:
+            if not self.use_arcface:
+                # (the reference downloads the pretrained tag, face_embedder.py:959-962; none exists
+                # offline: open_clip's init scheme, seeded - as ReIDEmbedder)
+                self._clip_params = clip_weights(clip_model_name, seed)
+                self.weights_source["clip_face"] = f"synthetic:{clip_model_name}:seed{seed}"
+                if callable(progress):
+                    progress(f"pcgpu: synthetic weights for OpenCLIP {clip_model_name} face embeddings "
+                             f"(no {clip_pretrained} checkpoint offline)")
+            elif arc_path:
                 self._arc_params, self._arc_depth, _ = onnx_models.load_arcface(arc_path)
                 self.weights_source["arcface"] = arc_path
             else:
@@ -355,27 +396,19 @@ class FaceEmbedder(YoloFaceBranch):
         # native pinned staging ring on a copy stream of their own (pc_frame_stage)
         self._h2d = get_context(self._device_index, "h2d")
         self._stage_threads = int(os.getenv("PERSON_CAPTURE_AMD_STAGE_THREADS", "8"))
-        self._arc = ArcFaceEngine(self._ectx, self._arc_params, self._arc_depth, precision=self.arc_precision,
-                                  max_batch=self._arc_batch)
-        # HIP graphs for net runs (unchanged callers' per-frame extract(): a SCRFD pass of one frame and
-        # an ArcFace pass of its faces are ~60 and ~100 small launches each; a C3 ArcFace quantum ~120):
-        # SCRFD runs of at most this many images and ArcFace runs of 4x as many rows replay a captured
-        # graph (bit-identical, the same launches). 128 (round 6; was 8): C3 1014 -> 1030 frames/s, C4 /
-        # C5 unchanged (profiles/r06aj_graph_batch_ab.txt). PERSON_CAPTURE_AMD_GRAPH_BATCH=0 launches eagerly
         self._graph_batch = int(os.getenv("PERSON_CAPTURE_AMD_GRAPH_BATCH", "128"))
-        if self._graph_batch > 0:
-            self._arc.net.set_graph(True, max_batch=4 * self._graph_batch)
-        self._arc_feat_dim = self._arc.dim
-        self._arc_fixed_batch = False
-        # resident block chains (one image per CU through the 14x14x256 stage) need whole CUs:
-        # beside the detection stream they lose to the per-conv kernels (measured C3 r03: 1705
-        # vs 1925 frames/s), so they run only when ArcFace has the device to itself. A chain
-        # round is one image per CU: 128 flip-TTA faces on 256 CUs.
-        if two and os.getenv("PERSON_CAPTURE_AMD_CHAIN", "auto") == "auto":
-            self._arc.net.set_chain_min_batch(0)
-        nch, min_b, per_round = self._arc.net.chain_info()
-        if nch > 0 and min_b < (1 << 30) and "PERSON_CAPTURE_AMD_EMBED_QUANTUM" not in os.environ:
-            self._embed_quantum = max(1, per_round // 2)
+        self._arc = self._clip = None
+        if not self.use_arcface:
+            # the OpenCLIP tower on the embed context; faces per tower run = its max batch, which is also
+            # the launch quantum at the end of a detection chunk (no flip pass, no conv round to fill)
+            self._clip_batch = max(1, int(os.getenv("PERSON_CAPTURE_AMD_FACE_CLIP_BATCH", "32")))
+            self._clip = ClipEngine(self._ectx, self._clip_params, clip_model_name, self.clip_precision,
+                                    self._clip_batch)
+            self._arc_feat_dim = self._clip.dim
+            if "PERSON_CAPTURE_AMD_EMBED_QUANTUM" not in os.environ:
+                self._embed_quantum = self._clip_batch
+        else:
+            self._init_arcface(two)
         # --- SCRFD probe controls (face_embedder.py:473-476) ---
         self.scrfd_tta_scales = (0.75, 0.60)
         self.scrfd_probe_conf_cap = 0.20
@@ -421,6 +454,30 @@ class FaceEmbedder(YoloFaceBranch):
             self.backend = "arcface"
             if callable(progress):
                 progress(f"YOLOv8-face(pcgpu) ready on cuda:{self._device_index}")
+
+    def _init_arcface(self, two: bool) -> None:
+        """The ArcFace engine on the embed context (`two`: beside the detection stream), its graphs,
+        chains and the embed quantum they imply."""
+        self._arc = ArcFaceEngine(self._ectx, self._arc_params, self._arc_depth, precision=self.arc_precision,
+                                  max_batch=self._arc_batch)
+        # HIP graphs for net runs (unchanged callers' per-frame extract(): a SCRFD pass of one frame and
+        # an ArcFace pass of its faces are ~60 and ~100 small launches each; a C3 ArcFace quantum ~120):
+        # SCRFD runs of at most this many images and ArcFace runs of 4x as many rows replay a captured
+        # graph (bit-identical, the same launches). 128 (round 6; was 8): C3 1014 -> 1030 frames/s, C4 /
+        # C5 unchanged (profiles/r06aj_graph_batch_ab.txt). PERSON_CAPTURE_AMD_GRAPH_BATCH=0 launches eagerly
+        if self._graph_batch > 0:
+            self._arc.net.set_graph(True, max_batch=4 * self._graph_batch)
+        self._arc_feat_dim = self._arc.dim
+        self._arc_fixed_batch = False
+        # resident block chains (one image per CU through the 14x14x256 stage) need whole CUs:
+        # beside the detection stream they lose to the per-conv kernels (measured C3 r03: 1705
+        # vs 1925 frames/s), so they run only when ArcFace has the device to itself. A chain
+        # round is one image per CU: 128 flip-TTA faces on 256 CUs.
+        if two and os.getenv("PERSON_CAPTURE_AMD_CHAIN", "auto") == "auto":
+            self._arc.net.set_chain_min_batch(0)
+        nch, min_b, per_round = self._arc.net.chain_info()
+        if nch > 0 and min_b < (1 << 30) and "PERSON_CAPTURE_AMD_EMBED_QUANTUM" not in os.environ:
+            self._embed_quantum = max(1, per_round // 2)
 
     # ------------------------------------------------------------------ knobs
     def set_prescan_fast(self, enable: bool, *, mode: str = "rr") -> None:
@@ -1171,11 +1228,15 @@ class FaceEmbedder(YoloFaceBranch):
         return (not getattr(self, "_fast_prescan", False)) or getattr(self, "_prescan_escalate", False)
 
     def _embed_per(self) -> int:
+        if not self.use_arcface:   # one tower row per face: _clip_encode has no flip pass
+            return self._clip.max_batch
         return self._arc.max_batch // 2 if self._do_flip() else self._arc.max_batch
 
     def _embed_launch(self, imgs: Sequence[Optional[_DevImage]], jobs: List[tuple], slot: int) -> tuple:
         """Enqueue crop + align/resize + quality + ArcFace (+ bank match) of at most one
         ArcFace batch of faces, and the readback into pinned memory."""
+        if not self.use_arcface:
+            return self._embed_launch_clip(imgs, jobs, slot)
         m = len(jobs)
         ctx = self._ectx
         chips = ctx.scratch("chips", m * _ARC_SIDE * _ARC_SIDE * 3)
@@ -1233,6 +1294,36 @@ class FaceEmbedder(YoloFaceBranch):
         if (2 * m if do_flip else m) > self._arc.max_batch:
             raise ValueError("embed launch larger than one ArcFace batch")
         self._arc.embed_device(chips.ptr, m, do_flip, fbuf.ptr)
+        return self._embed_readback(jobs, slot, chips, qbuf, fbuf)
+
+    def _embed_launch_clip(self, imgs: Sequence[Optional[_DevImage]], jobs: List[tuple], slot: int) -> tuple:
+        """_embed_launch with use_arcface=False (face_embedder.py:2454-2465): no alignment, landmarks
+        unused - every face box is one rectangle of a single pc_face_chips call; then quality, the
+        OpenCLIP preprocess + tower over the chips (one Pillow table: they are all 112 x 112), the
+        bank match and the same readback."""
+        m = len(jobs)
+        ctx = self._ectx
+        if m > self._clip.max_batch:
+            raise ValueError("embed launch larger than one OpenCLIP batch")
+        chips = ctx.scratch("chips", m * CHIP_BYTES)
+        geo = np.array([(imgs[fi].ptr + y1 * imgs[fi].stride + x1 * 3, y2 - y1, x2 - x1, imgs[fi].stride)
+                        for fi, (x1, y1, x2, y2), *_ in jobs], dtype=np.int64).reshape(-1, 4)
+        descs = imageops.chip_descs(geo[:, 0], geo[:, 1], geo[:, 2], geo[:, 3])
+        check(ctx.lib.pc_face_chips(ctx.handle, descs.ctypes.data_as(C.POINTER(ChipDesc)), m, chips.ptr),
+              ctx.handle, "face_chips")
+        qbuf = ctx.scratch("quality", m * 8)
+        check(ctx.lib.pc_face_quality(ctx.handle, chips.ptr, m, _ARC_SIDE, qbuf.ptr), ctx.handle,
+              "face_quality")
+        fbuf = ctx.scratch("feats", m * self._arc_feat_dim * 4)
+        self._clip.embed_device([(chips.ptr + j * CHIP_BYTES, _ARC_SIDE, _ARC_SIDE, _ARC_SIDE * 3) for j in range(m)],
+                                fbuf.ptr)
+        return self._embed_readback(jobs, slot, chips, qbuf, fbuf)
+
+    def _embed_readback(self, jobs: List[tuple], slot: int, chips, qbuf, fbuf) -> tuple:
+        """The bank match of an embed launch's features and its asynchronous readback."""
+        m = len(jobs)
+        ctx = self._ectx
+        chip_sz = CHIP_BYTES
         bank = getattr(self, "_bank", None)
         dbg = bool(getattr(self, "debug_chips", False))
         fd_bytes = m * 4 if bank is not None else 0
@@ -1244,7 +1335,7 @@ class FaceEmbedder(YoloFaceBranch):
         if bank is not None:
             dfd = ctx.scratch("fd", m * 4)
             didx = ctx.scratch("fd_idx", m * 4)
-            bank.match_device(fbuf.ptr, m, dfd.ptr, didx.ptr, ctx=ctx)
+            bank.match_device(fbuf.ptr, m, dfd.ptr, didx.ptr, feat_dim=self._arc_feat_dim, ctx=ctx)
             fd = ctx.download_async(dfd.ptr, pin, sizes[0] + sizes[1], (m,), np.float32)
         chip_h = None
         if dbg:
@@ -1329,6 +1420,8 @@ class FaceEmbedder(YoloFaceBranch):
         on device first, as _arcface_preprocess does)."""
         if not bgr_list:
             return []
+        if self._arc is None:
+            raise RuntimeError("no ArcFace net in this FaceEmbedder (use_arcface=False): _clip_encode embeds")
         m = len(bgr_list)
         chip_sz = _ARC_SIDE * _ARC_SIDE * 3
         ctx = self._ectx
@@ -1349,6 +1442,28 @@ class FaceEmbedder(YoloFaceBranch):
             k = min(per, m - s)
             self._arc.embed_device(chips.ptr + s * chip_sz, k, do_flip, fbuf.ptr + s * self._arc_feat_dim * 4)
         return ctx.download(fbuf.ptr, (m, self._arc_feat_dim), np.float32)
+
+    def _clip_encode(self, bgr_list: List[np.ndarray]):
+        """face_embedder.py:1649-1661: host BGR images of any size through open_clip's preprocess and
+        the tower -> [n][dim] unit float32 (no flip pass)."""
+        if not bgr_list:
+            return []
+        if self._clip is None:
+            raise RuntimeError("no OpenCLIP tower in this FaceEmbedder (use_arcface=True): _arcface_encode embeds")
+        ctx = self._ectx
+        n, dim, per = len(bgr_list), self._clip.dim, self._clip.max_batch
+        out = np.zeros((n, dim), np.float32)
+        for s0 in range(0, n, per):
+            devs = []
+            for k, b in enumerate(bgr_list[s0:s0 + per]):
+                a = np.ascontiguousarray(b, dtype=np.uint8)
+                d = ctx.scratch(f"cenc_src{k}", a.nbytes)
+                ctx.upload(a, d)
+                devs.append((d.ptr, a.shape[0], a.shape[1], a.strides[0]))
+            fbuf = ctx.scratch("cenc_feats", len(devs) * dim * 4)
+            self._clip.embed_device(devs, fbuf.ptr)
+            out[s0:s0 + len(devs)] = ctx.download(fbuf.ptr, (len(devs), dim), np.float32)
+        return out
 
     def _face_quality(self, bgr):
         b = np.ascontiguousarray(bgr, dtype=np.uint8)

@@ -177,6 +177,28 @@ def warp_descs(d_src, row_stride, w, h, M_fwd, d_dst, out_w: int = 112, out_h: i
     return d
 
 
+# pc_chip_desc (include/pcgpu.h) as a numpy record
+CHIP_DESC_DTYPE = np.dtype([("d_src", np.uint64), ("H", np.int32), ("W", np.int32), ("row_stride", np.int32),
+                            ("pad_", np.int32)])
+
+
+def chip_descs(d_src, H, W, row_stride) -> np.ndarray:
+    """pc_face_chips descriptors over arrays (one source rectangle per entry)."""
+    d = np.zeros(len(np.atleast_1d(d_src)), CHIP_DESC_DTYPE)
+    d["d_src"] = np.asarray(d_src, np.uint64)
+    d["H"], d["W"], d["row_stride"] = H, W, row_stride
+    return d
+
+
+def chip_plan(H: int, W: int) -> dict:
+    """The cv::resize path pc_face_chips takes for an H x W rectangle (native, host only): the `kind`,
+    `isx`, `isy` and `area_mode` of resize_plan(H, W, (112, 112), area=max(H, W) > 112)."""
+    out = (C.c_int32 * 4)()
+    if _lib.load().pc_face_chip_plan(int(H), int(W), out) != 0:
+        raise ValueError(f"face chip source {H} x {W}: sides of 1 .. 16384 pixels")
+    return {"kind": _lib.CHIP_KINDS[out[0]], "isx": out[1], "isy": out[2], "area_mode": out[3]}
+
+
 def estimate_affine_partial(src_sets: np.ndarray, dst: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """Batched cv2.estimateAffinePartial2D(src, dst, method=LMEDS) (native).
     src_sets [n][k][2] float32, dst [k][2] -> (M [n][2][3] float64, ok [n] bool)."""
