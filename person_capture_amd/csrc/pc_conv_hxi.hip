@@ -10,8 +10,10 @@
 // while group g's 18 k-steps (9 taps x two 32-channel blocks) run; one barrier per group, none inside.
 //  * output pixels are enumerated as ROWS x PITCH slots (the halo's pitch: the map width + 2 padding
 //    columns, rounded up to 16), so a tap is one slot offset for every 16-slot pixel fragment; the
-//    PITCH - HW columns past the map are computed and discarded (12.5 % at 14x14 - what the 256x224
-//    tile paid in idle CUs at batch 256 - and at 28x28);
+//    PITCH - HW columns past the map are computed and discarded: 12.5 % at pitch 16 / 32, 14 fragments
+//    for 196 pixels. The split 14x14x256 and 28x28x128 forms issue 13 (PC_HXI_DENSE, the default): the
+//    first on a dense enumeration of its own (HxiGeom DENSE), the second at pitch 29 (PC_HXI_28D below);
+//    the plain-f16, 7x7, one-workgroup-per-CU 28x28 and small-batch forms stay as described here;
 //  * 8 waves = WCH channel groups x WPX fragment groups; a wave's weight fragments come from the
 //    fragment-ordered copy (pc_net.cpp pack_wfrag) into registers a k-step ahead (double-buffered),
 //    its pixel fragments from the halo in groups of at most 7;
@@ -36,16 +38,22 @@ namespace pc {
 // tiles' order). Plain f16 (the BASELINE C2 fp16 net): a slot holds every input channel (CIN * 2 bytes),
 // staged once; K = (tap, 32-channel block), tap-major like conv_fast's plain tiles and the resident
 // chain, one MFMA per fragment pair - so it is bit-identical to them as well.
-template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT, int OCC>
+// DENSE (the 14x14 map at pitch 16): the fragments enumerate the image's 196 pixels, not the halo's 224
+// slots - 13 fragments (hxi_dense_pixel below).
+template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT, int OCC, bool DENSE = false>
 struct HxiGeom {
   static constexpr int NW = WCH * WPX, NT = 64 * NW;
-  static constexpr int NF = (ROWS * PITCH + 15) / 16;       // pixel fragments per workgroup (16 slots each)
-  static constexpr int TP = NF / WPX, TC = COUT / WCH / 16;
+  static constexpr int NPIX = ROWS * HW;
+  // pixel fragments per workgroup (16 slots, or 16 pixels, each)
+  static constexpr int NF = ((DENSE ? NPIX : ROWS * PITCH) + 15) / 16;
+  // (NF not a multiple of WPX: the last fragment group is one short, its waves skip their last fragment)
+  static constexpr int TP = (NF + WPX - 1) / WPX, TC = COUT / WCH / 16;
   static constexpr int CB = CIN / COUT;                      // channel blocks: workgroups per row block
   static constexpr int WPS = (NW * OCC + 3) / 4;             // waves per SIMD
   // fragments per read group (4 waves per SIMD - two 8-wave workgroups per CU: one at a time, the other
   // waves hide the reads)
-  static constexpr int TPG = WPS > 2 ? 1 : (TP > 7 ? (TP % 2 == 0 ? TP / 2 : TP) : TP);
+  static constexpr int TPG = WPS > 2 ? 1 : (TP > 7 ? (TP + 1) / 2 : TP);
+  static constexpr int NGRP = (TP + TPG - 1) / TPG;          // read groups (the last one short if TP is odd)
   // one wave per SIMD (the small-batch forms): no other wave hides a latency - the weights come 5 k-steps
   // ahead (not 1), and the pixel fragments of k-step k + 1 are read under k-step k's MFMAs (PF): 14x14 at
   // 12 images 34.9 -> 29.9 us. (Loader waves of their own for the halo pieces, 1-4 per workgroup, did not
@@ -55,14 +63,15 @@ struct HxiGeom {
   static constexpr int SB = SPLIT ? 256 : CIN * 2;           // halo slot bytes
   static constexpr int NB = SPLIT ? 2 : CIN / 32;            // 32-channel blocks per staged group
   static constexpr int NG = SPLIT ? CIN / 64 : 1, KPG = 9 * NB, NKS = NG * KPG;
-  // halo slots: the padded rows, + what the taps of the last fragment's discarded slots reach
-  static constexpr int SLOTS = (NF * 16 > ROWS * PITCH ? NF * 16 - ROWS * PITCH : 0) + (ROWS + 2) * PITCH + 2;
+  // halo slots: the padded rows, + what the taps of the last fragment's discarded slots reach; dense: up to
+  // the last pixel's last tap
+  static constexpr int SLOTS = DENSE ? (ROWS - 1) * PITCH + (HW - 1) + 2 * PITCH + 2 + 1
+                                     : (NF * 16 > ROWS * PITCH ? NF * 16 - ROWS * PITCH : 0) + (ROWS + 2) * PITCH + 2;
   static constexpr int PIECES = (SLOTS * SB + 1023) / 1024;
   static constexpr int STAGE = PIECES * 1024;
   // a 2-stage ring where the groups are several and two stages fit the workgroup's LDS share; else one
   // stage (at two workgroups per CU the other workgroup's MFMAs cover the exposed staging)
   static constexpr int NSTAGE = NG > 1 && 2 * STAGE * OCC <= 163840 ? 2 : 1;
-  static constexpr int NPIX = ROWS * HW;
   static constexpr int PC = COUT * NPIX * 4 <= 131072 / OCC ? COUT : COUT / 2;   // channels per epilogue pass
   static constexpr int NPASS = COUT / PC;
   static constexpr int RS = PC + 4;
@@ -71,18 +80,46 @@ struct HxiGeom {
   static constexpr int WTILE = SPLIT ? 2048 : 1024;          // packed weight bytes per K tile and 16-row block
   static constexpr int CGN = PC / 8;                         // 8-channel items per pixel and pass
   static constexpr int IT = (NPIX + NT / CGN - 1) / (NT / CGN);   // items (pixels) per thread and pass
-  static_assert(PITCH >= HW + 2 && NF % WPX == 0 && TP % TPG == 0, "pixel fragments");
+  // (a pitch of HW + 1: the right padding column of a row is the left one of the next)
+  static_assert(PITCH >= HW + 1 && (NF % WPX == 0 || TPG == 1) && !(PF && (DENSE || NF % WPX != 0)), "pixel fragments");
+  static_assert(DENSE ? WPX == 1 && SPLIT && HW == 14 && PITCH == 16 && ROWS == 14 && TPG == 7 : TP % TPG == 0,
+                "dense enumeration");
   static_assert(COUT % (16 * WCH) == 0 && CIN % 64 == 0 && HW % ROWS == 0 && SB % 256 == 0, "tiling");
   static_assert(SMEM <= 163840, "LDS");
   static_assert(NPASS == 1 || WCH % 2 == 0, "epilogue passes split the channel waves");
 };
 
+// The dense enumeration of a 14x14 image in 13 fragments: output pixel (row, col) of fragment f's lane slot fr
+// (col = 14: a discarded lane). The halo slot of a pixel at tap (0, 0) is 16 row + col.
+//  * fragments 0-6: columns 0-7 of rows 2 f (lanes 0-7) and 2 f + 1 (lanes 8-15): slot 32 f + fr + (fr & 8).
+//    The 8 slots that a ds_read_b128 lane group reads at one chunk parity (lane slots 0-3 and 12-15, or
+//    4-11) have 8 different keys: conflict-free, as 16 consecutive slots are;
+//  * fragments 7-12, j = f - 7: columns 8-13 of rows 2 j (lanes 0-5) and 2 j + 1 (lanes 8-13): slot
+//    32 j + 8 + fr + (fr & 8), the same lane offset; lanes 6 and 7 take a pair of the 12 pixels left in
+//    columns 8-13 of rows 12 and 13 - row 12 + j / 3, columns 8 + 2 (j % 3) and the next; lanes 14 and 15
+//    are discarded and read the row's padding columns 14 and 15. The pair's keys are those of two other
+//    lanes of its group: a 2-way conflict in every group of these 6 fragments' reads. Columns 8-13 share
+//    their keys with columns 0-5, so 13 fragments cannot hold 196 pixels without a conflict
+//    (tests/test_hxi_dense_cpu.py); the plain enumeration q = 16 f + fr has it in 12 fragments and needs
+//    per-fragment lane offsets: 142.5 us per layer at 256 images for the pitch enumeration's 134.8
+//    (profiles/r08_hxi_dense_layers_ab.txt).
+__device__ __forceinline__ void hxi_dense_pixel(int f, int fr, int& row, int& col) {
+  if (f < 7) {
+    row = 2 * f + (fr >> 3), col = fr & 7;
+  } else {
+    const int j = f - 7, c = fr & 7;
+    if (c < 6) row = 2 * j + (fr >> 3), col = 8 + c;
+    else if (fr < 8) row = 12 + j / 3, col = 8 + 2 * (j % 3) + (fr & 1);
+    else row = 0, col = 14;
+  }
+}
+
 // One layer for this workgroup's rows: `p` is the launch's kernel argument (conv_hxi) or one entry of a
 // chained launch's layer array (conv_hxi_chain, read through the constant address space - the array is
 // uploaded once at plan time and never written while a kernel runs); N is the batch (the grid).
-template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT, int OCC, class P>
+template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT, int OCC, bool DENSE, class P>
 __device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid, char* smem) {
-  using G = HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC>;
+  using G = HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC, DENSE>;
   constexpr int NW = G::NW, NT = G::NT, TC = G::TC, TP = G::TP, TPG = G::TPG, NG = G::NG, NKS = G::NKS;
   constexpr int STAGE = G::STAGE, PIECES = G::PIECES, SB = G::SB, NB = G::NB, KPG = G::KPG;
   static_assert(G::SMEM * OCC <= 163840, "LDS for OCC workgroups per CU");
@@ -163,7 +200,12 @@ __device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid,
   // (recomputed at each k-step - the asm keeps the compiler from hoisting all (tap, block) offsets of
   // the unrolled loop into registers at once: 24 of them in the plain 256-channel form)
   auto boff = [&](int sh, int chunk) __attribute__((always_inline)) {
-    const int h = fr + sh;
+    int h = fr;
+    // (a pitch that puts the row shift into sh has 9 shifts x 4 chunks of these: at 128 registers the lane
+    // slot is made opaque as well, or the compiler computes them once for all channel groups and spills the
+    // 28x28 form at pitch 29: 76 bytes of scratch)
+    if constexpr (PITCH % 8 != 0 && G::WPS > 2) asm volatile("" : "+v"(h));
+    h += sh;
     unsigned v = (unsigned)(h * SB + ((chunk ^ ((h & 7) << 1)) << 4));
     asm volatile("" : "+v"(v));
     return v;
@@ -172,6 +214,11 @@ __device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid,
   // 16 f .. 16 f + 15 (slot o = output row o / PITCH, column o % PITCH; columns >= HW and rows >= ROWS are
   // discarded - a pitch that is not a multiple of 16 lets a fragment span two rows: the 7x7 form's 9)
   auto fslot = [&](int t) __attribute__((always_inline)) { return (wpx * TP + t) * 16; };
+  // dense: the byte of slot h's chunk in the stage, ck = (blk * 4 + kg) << 4 the chunk's byte in an unswizzled
+  // slot (the key touches bits 5-7 only; the lo chunk is 128 bytes from the hi one)
+  auto dswz = [](int h, unsigned ck) __attribute__((always_inline)) {
+    return ((unsigned)h << 8) | ((((unsigned)h << 5) & 0xe0u) ^ ck);
+  };
   static_for<NG>([&](auto gc) __attribute__((always_inline)) {
     constexpr int g = decltype(gc)::value, st = G::NSTAGE == 2 ? (g & 1) : 0;
     if constexpr (G::NSTAGE == 1 && g > 0) {   // one stage: group g replaces g - 1 once every wave is done
@@ -192,7 +239,7 @@ __device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid,
       // (pitches that are multiples of 8 keep the row shift out of the swizzled offset: fewer live offsets -
       // folding it in spilled the two-workgroup 28x28 form)
       constexpr int sh = PITCH % 8 == 0 ? dx : dy * PITCH + dx, rsh = PITCH % 8 == 0 ? dy * PITCH : 0;
-      const unsigned oh = boff(sh, blk * 4 + kg), ol = SPLIT ? boff(sh, 8 + blk * 4 + kg) : 0u;
+      const unsigned oh = DENSE ? 0u : boff(sh, blk * 4 + kg), ol = SPLIT && !DENSE ? boff(sh, 8 + blk * 4 + kg) : 0u;
       if (p.dbg & 2) return;   // tuning only: no MFMAs
       if constexpr (G::PF) {
         // the hi fragments were read at the previous k-step (the group's first: here), the lo ones at the top
@@ -236,9 +283,70 @@ __device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid,
         __builtin_amdgcn_sched_barrier(0);
         return;
       }
-      static_for<TP / TPG>([&](auto pc) __attribute__((always_inline)) {
-        constexpr int t0 = decltype(pc)::value * TPG;
+      unsigned odn[DENSE ? TPG : 1];   // (dense: the second read group's lane offsets, computed under the first's MFMAs)
+      static_for<G::NGRP>([&](auto pc) __attribute__((always_inline)) {
+        constexpr int t0 = decltype(pc)::value * TPG, CNT = TP - t0 < TPG ? TP - t0 : TPG;
+        if constexpr (G::NF % WPX != 0) {   // (wave-uniform: the short fragment group's last fragment)
+          if (wpx * TP + t0 >= G::NF) return;
+        }
         f16x8 bh[TPG], bl[SPLIT ? TPG : 1];
+        if constexpr (DENSE) {
+          // the lane slot's halo slot less the fragment's first (hxi_dense_pixel): fr + (fr & 8) for the lanes of
+          // the two row runs - one offset for every fragment, as at the pitch enumeration; lanes 6 and 7 of the
+          // fragments 7-12 have a slot of their own. Recomputed from an opaque lane slot at each k-step (hoisted
+          // over the unrolled K loop the offsets do not fit the registers); those of fragments 7-12 in the
+          // first read group, spread over its last MFMA pass (after it they held the wave's MFMAs back)
+          unsigned od[TPG];
+          int e = fr;
+          asm volatile("" : "+v"(e));
+          const unsigned ck = (unsigned)(blk * 4 + kg) << 4;
+          const unsigned om = dswz(e + (e & 8) + dx, ck);
+          auto imm = [](int f) __attribute__((always_inline)) { return f < 7 ? 32 * f : 32 * (f - 7) + 8; };
+          static_for<CNT>([&](auto tc) __attribute__((always_inline)) {
+            constexpr int t = decltype(tc)::value, f = t0 + t;
+            od[t] = f < 7 ? om : odn[t];
+            bh[t] = *reinterpret_cast<const f16x8*>(base + od[t] + (imm(f) + dy * PITCH) * SB);
+          });
+#pragma unroll
+          for (int a = 0; a < TC; ++a)
+#pragma unroll
+            for (int t = 0; t < CNT; ++t)
+              acc[a][t0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wbl[q][a], bh[t], acc[a][t0 + t], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          static_for<CNT>([&](auto tc) __attribute__((always_inline)) {
+            constexpr int t = decltype(tc)::value, f = t0 + t;
+            constexpr int im = f < 7 ? 32 * f : 32 * (f - 7) + 8;
+            bl[t] = *reinterpret_cast<const f16x8*>(base + (od[t] ^ 128u) + (im + dy * PITCH) * SB);
+          });
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int a = 0; a < TC; ++a)
+#pragma unroll
+            for (int t = 0; t < CNT; ++t)
+              acc[a][t0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wbh[q][a], bh[t], acc[a][t0 + t], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (t0 == 0) {
+            static_for<TP - TPG>([&](auto tc) __attribute__((always_inline)) {
+              constexpr int t = decltype(tc)::value, j = t, f = 7 + j;
+              constexpr int X = (12 + j / 3) * PITCH + 8 + 2 * (j % 3);   // the pair's first slot
+              odn[t] = (e & 14) == 6 ? dswz((e & 1) + (X - imm(f)) + dx, ck) : om;
+            });
+          }
+#pragma unroll
+          for (int a = 0; a < TC; ++a)
+#pragma unroll
+            for (int t = 0; t < CNT; ++t)
+              acc[a][t0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wbh[q][a], bl[t], acc[a][t0 + t], 0, 0, 0);
+          if constexpr (t0 == 0) {   // (one MFMA, then 4 of the offsets' VALU operations)
+#pragma unroll
+            for (int i = 0; i < TC * CNT; ++i) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          return;
+        }
 #pragma unroll
         for (int t = 0; t < TPG; ++t)
           bh[t] = *reinterpret_cast<const f16x8*>(base + oh + (fslot(t0 + t) + rsh) * SB);
@@ -346,8 +454,13 @@ __device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid,
       for (int a = 0; a < TC; ++a)
 #pragma unroll
         for (int t = 0; t < TP; ++t) {
-          const int o = (wpx * TP + t) * 16 + fr;
-          const int orow = o / PITCH, ocol = o % PITCH;
+          int orow, ocol;
+          if constexpr (DENSE) {
+            hxi_dense_pixel(t, fr, orow, ocol);
+          } else {
+            const int o = (wpx * TP + t) * 16 + fr;
+            orow = o / PITCH, ocol = o % PITCH;
+          }
           if (ocol < HW && orow < ROWS) {
             const int pl = orow * HW + ocol;
             const int cl = (NPASS == 1 ? wch : wch % (WCH / 2)) * TC * 16 + a * 16 + kg * 4;
@@ -415,10 +528,10 @@ __device__ __forceinline__ void conv_hxi_layer(P& p, const int N, const int tid,
   }
 }
 
-template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT = true, int OCC = 1>
+template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool SPLIT = true, int OCC = 1, bool DENSE = false>
 __global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX * OCC + 3) / 4) void conv_hxi(ConvParams p) {
-  __shared__ __attribute__((aligned(16))) char smem[HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC>::SMEM];
-  conv_hxi_layer<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC>(p, p.N, (int)threadIdx.x, smem);
+  __shared__ __attribute__((aligned(16))) char smem[HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC, DENSE>::SMEM];
+  conv_hxi_layer<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, SPLIT, OCC, DENSE>(p, p.N, (int)threadIdx.x, smem);
 }
 
 // A run of consecutive layers of the one-image-per-workgroup split forms (14x14x256, 7x7x512) as one
@@ -436,9 +549,9 @@ __global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX * OCC + 3) / 4) void con
 // or L2 write-back, and no device-scope flush is needed (LLVM AMDGPUUsage, "Memory Model gfx942":
 // workgroup-scope release / acquire fences in non-tgsplit mode are s_waitcnt only).
 // The barrier also keeps the next layer's first halo stage off the LDS image a slower wave still reads.
-template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX>
+template <int HW, int PITCH, int ROWS, int CIN, int COUT, int WCH, int WPX, bool DENSE = false>
 __global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX + 3) / 4) void conv_hxi_chain(const ConvParams* lp, int nl) {
-  __shared__ __attribute__((aligned(16))) char smem[HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, true, 1>::SMEM];
+  __shared__ __attribute__((aligned(16))) char smem[HxiGeom<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, true, 1, DENSE>::SMEM];
   typedef const __attribute__((address_space(4))) ConvParams CP;
   CP* cp = (CP*)lp;
   for (int l = 0; l < nl; ++l) {
@@ -452,7 +565,7 @@ __global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX + 3) / 4) void conv_hxi_
     // derived from it stay live through the K loop and spill the 14x14 form, 233 registers as it is)
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    conv_hxi_layer<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, true, 1>(cp[l], (int)gridDim.x, tid, smem);
+    conv_hxi_layer<HW, PITCH, ROWS, CIN, COUT, WCH, WPX, true, 1, DENSE>(cp[l], (int)gridDim.x, tid, smem);
   }
 }
 
@@ -461,6 +574,13 @@ __global__ __launch_bounds__(64 * WCH * WPX, (WCH * WPX + 3) / 4) void conv_hxi_
 // 28x28x128 at two workgroups per CU (its halo stage is 73 KB)
 #define PC_HXI_14 14, 16, 14, 256, 256, 8, 1
 #define PC_HXI_28 28, 32, 7, 128, 128, 4, 2
+// the split forms without padding columns in the fragments (PC_HXI_DENSE, the default):
+// 196 pixels per workgroup in 13 fragments for the pitch enumeration's 14.
+//  * 14x14x256: the dense enumeration over the same halo (HxiGeom DENSE, hxi_dense_pixel);
+//  * 28x28x128: pitch 29 - the right padding column of row y is the left one of row y + 1, the 7 rows are
+//    203 consecutive slots, a fragment spans two rows as in the 7x7 form; 16 consecutive slots stay
+//    conflict-free. The two fragment groups take 7 and 6 fragments.
+#define PC_HXI_28D 28, 29, 7, 128, 128, 4, 2
 // 7x7x512 (the last stage, split only): one image per workgroup at pitch 9 - 63 slots in 4 fragments
 // (77 % kept; a pitch of 16 would keep 44 %), 8 x 1 waves of 64 channels x 4 fragments
 #define PC_HXI_7 7, 9, 7, 512, 512, 8, 1
@@ -488,7 +608,8 @@ int conv_hxi_ok(const ConvParams& p) {
          p.wfrag != nullptr && (!split || p.ysplit == C);
 }
 
-hipError_t conv_hxi_launch(const ConvParams& p, int small, int occ1_28, hipStream_t s) {
+// (dense: Tuning::hxi_dense, read when the net is built)
+hipError_t conv_hxi_launch(const ConvParams& p, int small, int occ1_28, int dense, hipStream_t s) {
   if (!conv_hxi_ok(p)) return hipErrorInvalidValue;
   const bool split = p.ysplit != 0;
   if (small) {   // (16 workgroups per image; split only)
@@ -501,12 +622,14 @@ hipError_t conv_hxi_launch(const ConvParams& p, int small, int occ1_28, hipStrea
     hipLaunchKernelGGL((conv_hxi<PC_HXI_7, true, 1>), dim3(p.N), dim3(512), 0, s, p);
   } else if (p.OH == 14) {
     // (half an image per workgroup at two per CU, 7 rows: 147.7 vs 145.3 us, profiles/r06t_hxi14_half_ab.txt)
-    if (split) hipLaunchKernelGGL((conv_hxi<PC_HXI_14, true, 1>), dim3(p.N), dim3(512), 0, s, p);
+    if (split && (dense & kHxiDense14)) hipLaunchKernelGGL((conv_hxi<PC_HXI_14, true, 1, true>), dim3(p.N), dim3(512), 0, s, p);
+    else if (split) hipLaunchKernelGGL((conv_hxi<PC_HXI_14, true, 1>), dim3(p.N), dim3(512), 0, s, p);
     else hipLaunchKernelGGL((conv_hxi<PC_HXI_14, false, 1>), dim3(p.N), dim3(512), 0, s, p);
   } else {
     // (split: two workgroups per CU, one halo stage each, so one's epilogue runs under the other's MFMAs;
     // PC_HXI28_OCC=1 the 2-stage form, read when the net is built: pc_plan.cpp)
     if (split && occ1_28) hipLaunchKernelGGL((conv_hxi<PC_HXI_28, true, 1>), dim3(p.N * 4), dim3(512), 0, s, p);
+    else if (split && (dense & kHxiDense28)) hipLaunchKernelGGL((conv_hxi<PC_HXI_28D, true, 2>), dim3(p.N * 4), dim3(512), 0, s, p);
     else if (split) hipLaunchKernelGGL((conv_hxi<PC_HXI_28, true, 2>), dim3(p.N * 4), dim3(512), 0, s, p);
     else hipLaunchKernelGGL((conv_hxi<PC_HXI_28, false, 2>), dim3(p.N * 4), dim3(512), 0, s, p);
   }
@@ -520,10 +643,11 @@ int conv_hxi_chain_ok(const ConvParams& p) {
 
 // nl layers (d_layers: ConvParams[nl] on the device, each conv_hxi_chain_ok, all of one map size HW) for
 // N images as one launch
-hipError_t conv_hxi_chain_launch(const void* d_layers, int nl, int HW, int N, hipStream_t s) {
+hipError_t conv_hxi_chain_launch(const void* d_layers, int nl, int HW, int N, int dense, hipStream_t s) {
   if (!d_layers || nl < 1 || N < 1) return hipErrorInvalidValue;
   const ConvParams* lp = static_cast<const ConvParams*>(d_layers);
-  if (HW == 14) hipLaunchKernelGGL((conv_hxi_chain<PC_HXI_14>), dim3(N), dim3(512), 0, s, lp, nl);
+  if (HW == 14 && (dense & kHxiDense14)) hipLaunchKernelGGL((conv_hxi_chain<PC_HXI_14, true>), dim3(N), dim3(512), 0, s, lp, nl);
+  else if (HW == 14) hipLaunchKernelGGL((conv_hxi_chain<PC_HXI_14>), dim3(N), dim3(512), 0, s, lp, nl);
   else if (HW == 7) hipLaunchKernelGGL((conv_hxi_chain<PC_HXI_7>), dim3(N), dim3(512), 0, s, lp, nl);
   else return hipErrorInvalidValue;
   return hipGetLastError();

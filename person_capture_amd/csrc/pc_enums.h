@@ -17,4 +17,7 @@ enum T2dFlags {
   kT2d128x8 = 32,     // PC_T2D_128=8
 };
 
+// conv_hxi's split forms without padding columns in their pixel fragments (Tuning::hxi_dense, PC_HXI_DENSE)
+enum HxiDense { kHxiDense14 = 2, kHxiDense28 = 4 };
+
 }  // namespace pc

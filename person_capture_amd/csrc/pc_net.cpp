@@ -15,9 +15,9 @@ hipError_t conv_halo_launch(int f32, int cfg, const ConvParams& p, hipStream_t s
 hipError_t conv_fast_launch(int f32, int rowb, int cfg, const ConvParams& p, int wg_layout, hipStream_t s);
 hipError_t conv_hx_launch(const ConvParams& p, int wlds, hipStream_t s);
 hipError_t conv_hxg_launch(const ConvParams& p, int small, hipStream_t s);
-hipError_t conv_hxi_launch(const ConvParams& p, int small, int occ1_28, hipStream_t s);
+hipError_t conv_hxi_launch(const ConvParams& p, int small, int occ1_28, int dense, hipStream_t s);
 int conv_hxi_chain_ok(const ConvParams& p);
-hipError_t conv_hxi_chain_launch(const void* d_layers, int nl, int HW, int N, hipStream_t s);
+hipError_t conv_hxi_chain_launch(const void* d_layers, int nl, int HW, int N, int dense, hipStream_t s);
 hipError_t conv_t2d_launch(const ConvParams& p, int variant, hipStream_t s);
 hipError_t conv_chain_launch(const void* x, int xcs, void* y, int ycs, const void* blk_dev, int nblk, int N, int H,
                              int W, long long ktot, int dbg, hipStream_t s);
@@ -734,7 +734,7 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
     if ((rc = prof_begin(n, prof, open_ev, rec))) return rc;
     if (run) {
       rec.small = cls;
-      HIPCHK(c, conv_hxi_chain_launch(static_cast<const ConvParams*>(hr->d_params) + run->param_off, run->nl, run->hw, N, s));
+      HIPCHK(c, conv_hxi_chain_launch(static_cast<const ConvParams*>(hr->d_params) + run->param_off, run->nl, run->hw, N, tu.hxi_dense, s));
       i += run->nl - 1;
     } else if (op.kind == OP_CONV) {
       const ConvPlan& pl = cls >= 0 ? n->plans_cls[cls][i] : n->plans[i];
@@ -742,7 +742,7 @@ static int run_ops(pc_net* n, int N, hipStream_t s) {
       ConvParams p;
       conv_params(n, i, pl, N, p);
       if (pl.hx >= 3 && pl.hx != 5) {
-        HIPCHK(c, conv_hxi_launch(p, pl.hx >= 7, tu.hxi28_occ1, s));
+        HIPCHK(c, conv_hxi_launch(p, pl.hx >= 7, tu.hxi28_occ1, tu.hxi_dense, s));
       } else if (pl.hx == 2 || pl.hx == 5) {
         HIPCHK(c, conv_hxg_launch(p, pl.hx == 5, s));
       } else if (pl.hx) {

@@ -150,6 +150,9 @@ struct Tuning {
   // (profiles/r07a_hxi_chain_cap_sweep.txt)
   int hxi_chain_max = 8;
   int hxi28_occ1 = 0;         // PC_HXI28_OCC=1: the 28x28 split form at one workgroup per CU
+  // PC_HXI_DENSE: the split 14x14 / 28x28 forms' fragments without padding columns (kHxiDense14 | kHxiDense28;
+  // 0: the halo's pitch for both, 1 or not given: both dense, 2 / 4: one of them)
+  int hxi_dense = 6;
   // --- launch-time forms ---
   int conv_dbg_set = 0;       // PC_CONV_DBG given (phase splits: no chained conv_hxi launches)
   int conv_dbg = 0;           // its value (ConvParams::dbg)

@@ -61,6 +61,7 @@ Tuning tuning_from_env() {
   if (given("PC_CHAIN_MODE")) t.chain_mode = num("PC_CHAIN_MODE", 0) ? 1 : 0;
   if (given("PC_HXI_CHAIN_MAX")) t.hxi_chain_max = std::max(0, num("PC_HXI_CHAIN_MAX", 0));
   t.hxi28_occ1 = is("PC_HXI28_OCC", 1);
+  if (given("PC_HXI_DENSE")) t.hxi_dense = is("PC_HXI_DENSE", 1) ? kHxiDense14 | kHxiDense28 : num("PC_HXI_DENSE", 0) & (kHxiDense14 | kHxiDense28);
 
   t.conv_dbg_set = given("PC_CONV_DBG");
   t.conv_dbg = num("PC_CONV_DBG", 0);
