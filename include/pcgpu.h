@@ -36,6 +36,10 @@
  *   pc_face_chips                      the unaligned face chips of the OpenCLIP face mode: cv2.resize(face_bgr,
  *                                      (112,112), INTER_AREA if max(h,w) > 112 else INTER_LINEAR) per kept face
  *                                      (face_embedder.py:2454-2460, 2132-2141), all faces of a batch at once
+ *   pc_nv12_to_bgr                     FfmpegPipeReader._nv12_to_bgr (video_io.py:2888-2912), the conversion of
+ *                                      the NV12 pipe format (PC_PIPE_PIXFMT=nv12, video_io.py:1225-1228, 1901-1904)
+ *   pc_nv12_resize_area_batch /        the same conversion followed by the pre-scan's cv2.resize(..., INTER_AREA)
+ *   pc_nv12_resize_area_fast_batch     (gui_app.py:1505-1507) in one pass, no full-size BGR frame in between
  *   pc_yolo_detect                     PersonDetector.detect -> [ext] ultralytics YOLO.predict(conf, iou=0.45,
  *                                      classes=[0], max_det=40, imgsz=640) (detectors.py:271-296)
  *   pc_yolo_pose_detect                FaceEmbedder YOLOv8-face backend (Y8F_DEFAULT, face_embedder.py:33) ->
@@ -168,6 +172,19 @@ typedef struct pc_chip_desc {
 #define PC_CHIP_LINEAR 3    /* bilinear; area_mode 1 when INTER_AREA was asked but an axis upscales */
 #define PC_CHIP_SIDE 112
 #define PC_CHIP_MAX_SIDE 16384
+
+/* One NV12 frame of pc_nv12_to_bgr on the device: the Y plane (H rows of W bytes, y_stride apart), the
+ * interleaved U, V plane (H / 2 rows of W bytes, uv_stride apart) and the BGR u8 destination (H rows of
+ * 3 W bytes, dst_stride apart). H and W even, 2 .. PC_NV12_MAX_SIDE. */
+typedef struct pc_nv12_desc {
+  const uint8_t* d_y;
+  const uint8_t* d_uv;
+  int32_t H, W, y_stride, uv_stride;
+  uint8_t* d_dst;
+  int32_t dst_stride;
+  int32_t pad_;
+} pc_nv12_desc;
+#define PC_NV12_MAX_SIDE 16384
 
 /* One crop of the dataset curator's metrics batch (pc_crop_metrics): a BGR u8 image on the device and
  * the geometry of its two INTER_AREA targets, [0] the <= 256 plane of sharpness_norm (w2 x h2;
@@ -334,6 +351,29 @@ int pc_face_chip_plan(int H, int W, int32_t* h_out4);
  * device. n == 0: PC_OK, nothing enqueued. A null pointer, H or W outside [1, PC_CHIP_MAX_SIDE],
  * row_stride < 3 W or n < 0: PC_ERR_ARG before anything is enqueued. */
 int pc_face_chips(pc_ctx* ctx, const pc_chip_desc* h_descs, int n, uint8_t* d_chips);
+/* FfmpegPipeReader._nv12_to_bgr (video_io.py:2888-2912) for n NV12 frames of any mix of sizes in one
+ * launch: each chroma sample serves its 2 x 2 pixels; in f32 with every operation rounded once (no fused
+ * multiply-add), C = y - 16, D = u - 128, E = v - 128, r = k0 C + k1 E, g = (k0 C - k2 D) - k3 E,
+ * b = k0 C + k4 D with k = (1.16438356, 1.79274107, 0.21324861, 0.53290933, 2.11240179) rounded to f32,
+ * clamped to [0, 255], truncated, stored B, G, R. Frames whose pointers and strides are all multiples of 16
+ * move 16 bytes per load and store; others (and the last W % 16 pixels of a row) go byte by byte. Nothing
+ * outside [row, row + W) of a source row is read, nothing outside [row, row + 3 W) of a destination row
+ * written. n == 0: PC_OK, nothing enqueued. A null pointer, an odd size or one outside [2, PC_NV12_MAX_SIDE],
+ * y_stride < W, uv_stride < W, dst_stride < 3 W or n < 0: PC_ERR_ARG before anything is staged or enqueued. */
+int pc_nv12_to_bgr(pc_ctx* ctx, const pc_nv12_desc* h_descs, int n);
+/* pc_nv12_to_bgr followed by pc_resize_area_batch (the pre-scan's downscale, gui_app.py:1505-1507, of
+ * frames the NV12 pipe delivered, video_io.py:2888-2912) for n equally sized H x W NV12 frames, without
+ * the full-size BGR frame: every output pixel is the INTER_AREA sum over source pixels converted in
+ * registers, so the bytes equal the two calls'. h_ys / h_uvs / h_dsts: host arrays of n device pointers
+ * (destination OH x OW x 3 contiguous); tables as pc_resize_area, every source index checked against H, W. */
+int pc_nv12_resize_area_batch(pc_ctx* ctx, const uint8_t* const* h_ys, const uint8_t* const* h_uvs,
+                              uint8_t* const* h_dsts, int n, int H, int W, int y_stride, int uv_stride,
+                              const pc_area_tab* h_xtab, const int32_t* h_xstart, int n_x, const pc_area_tab* h_ytab,
+                              const int32_t* h_ystart, int n_y, int OH, int OW);
+/* The same at an exact integer ratio isx x isy (pc_resize_area_fast's arithmetic; OW isx <= W, OH isy <= H). */
+int pc_nv12_resize_area_fast_batch(pc_ctx* ctx, const uint8_t* const* h_ys, const uint8_t* const* h_uvs,
+                                   uint8_t* const* h_dsts, int n, int H, int W, int y_stride, int uv_stride, int isx,
+                                   int isy, int OH, int OW);
 
 /* ---- detection ---- */
 /* Runs letterbox -> SCRFD net -> decode(score >= det_thresh) -> NMS(nms_thresh) for n frames.

@@ -77,6 +77,15 @@ class ChipDesc(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class Nv12Desc(C.Structure):
+    _fields_ = [("d_y", C.c_void_p), ("d_uv", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
+                ("y_stride", C.c_int32), ("uv_stride", C.c_int32), ("d_dst", C.c_void_p),
+                ("dst_stride", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(Nv12Desc) == 48
+PC_NV12_MAX_SIDE = 16384
+
 PC_CHIP_COPY, PC_CHIP_AREA_FAST, PC_CHIP_AREA, PC_CHIP_LINEAR = 0, 1, 2, 3
 CHIP_KINDS = {PC_CHIP_COPY: "copy", PC_CHIP_AREA_FAST: "area_fast", PC_CHIP_AREA: "area", PC_CHIP_LINEAR: "linear"}
 CHIP_BYTES = 112 * 112 * 3
@@ -155,6 +164,10 @@ SIGNATURES = {
                               C.POINTER(C.c_int32), _I, _I, _I], _I),
     "pc_face_chip_plan": ([_I, _I, C.POINTER(C.c_int32)], _I),
     "pc_face_chips": ([_P, C.POINTER(ChipDesc), _I, _P], _I),
+    "pc_nv12_to_bgr": ([_P, C.POINTER(Nv12Desc), _I], _I),
+    "pc_nv12_resize_area_batch": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(AreaTab), C.POINTER(C.c_int32), _I,
+                                   C.POINTER(AreaTab), C.POINTER(C.c_int32), _I, _I, _I], _I),
+    "pc_nv12_resize_area_fast_batch": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I], _I),
     "pc_scrfd_detect": ([_P, C.POINTER(LetterboxDesc), _I, _I, _F, _F, C.POINTER(_F), _I, _P, _P, _P, _P], _I),
     "pc_embed_finalize": ([_P, _P, _I, _I, _I, _I, _P], _I),
     "pc_arcface_embed": ([_P, _P, _I, _I, _P], _I),

@@ -41,6 +41,13 @@ hipError_t resize_area_rows_launch(const void* jobs, int n, int row_stride, cons
                                   const AreaTab* ytab, const int* ystart, int OH, int OW, int span_bytes,
                                   hipStream_t s);
 hipError_t face_chips_launch(const void* d_jobs, int n, hipStream_t s);
+// pc_nv12.hip
+hipError_t nv12_to_bgr_launch(const void* d_jobs, int n, long long nwg, hipStream_t s);
+hipError_t nv12_resize_area_launch(const void* d_jobs, int n, int y_stride, int uv_stride, const AreaTab* xtab,
+                                   const int* xstart, const AreaTab* ytab, const int* ystart, int OH, int OW,
+                                   hipStream_t s);
+hipError_t nv12_resize_area_fast_launch(const void* d_jobs, int n, int y_stride, int uv_stride, int isx, int isy,
+                                        int OH, int OW, hipStream_t s);
 hipError_t curate_metrics_launch(const void* d_imgs, int n, const void* d_bands, int nbands, const void* d_tabs,
                                  const int* d_starts, const double* d_dct, int max_pixels, hipStream_t s);
 hipError_t sim_matrix_launch(const float* F, int n, int dim, float* S, hipStream_t s);
@@ -105,6 +112,7 @@ static_assert(sizeof(pc_area_tab) == 12, "area tab layout");
 static_assert(sizeof(pc_curate_desc) == 72 && sizeof(pc_curate_record) == 1312, "curate layouts");
 static_assert(sizeof(pc_resize_desc) == 80, "resize desc layout");
 static_assert(sizeof(pc_chip_desc) == 24, "chip desc layout");
+static_assert(sizeof(pc_nv12_desc) == 48, "nv12 desc layout");
 static_assert(sizeof(pc_yolo_letterbox_desc) == 64, "yolo letterbox desc layout");
 static_assert(sizeof(pc_yolo_scale) == 20, "yolo scale layout");
 
@@ -665,6 +673,109 @@ extern "C" int pc_face_chips(pc_ctx* c, const pc_chip_desc* h, int n, uint8_t* d
   int rc = stage_copy(c, jobs.data(), sizeof(Job) * (size_t)n, &dj);
   if (rc) return rc;
   HIPCHK(c, face_chips_launch(dj, n, c->stream));
+  return PC_OK;
+}
+
+// ---- NV12 frames (pc_nv12.hip) ----
+static bool nv12_size_ok(int H, int W) {
+  return H >= 2 && W >= 2 && H <= PC_NV12_MAX_SIDE && W <= PC_NV12_MAX_SIDE && !(H & 1) && !(W & 1);
+}
+
+extern "C" int pc_nv12_to_bgr(pc_ctx* c, const pc_nv12_desc* h, int n) {
+  if (!c) return PC_ERR_ARG;
+  if (n < 0 || (n > 0 && !h)) return fail(c, PC_ERR_ARG, "pc_nv12_to_bgr: bad arguments");
+  if (n == 0) return PC_OK;
+  struct Job {   // pc_nv12.hip Nv12Job
+    const uint8_t *y, *uv; uint8_t* dst;
+    int32_t H, W, y_stride, uv_stride, dst_stride, aligned, ux, wg0;
+  };
+  static_assert(sizeof(Job) == 56, "nv12 job layout");
+  std::vector<Job> jobs((size_t)n);
+  long long nwg = 0;
+  for (int i = 0; i < n; ++i) {
+    const pc_nv12_desc& d = h[i];
+    if (!d.d_y || !d.d_uv || !d.d_dst || !nv12_size_ok(d.H, d.W) || d.y_stride < d.W || d.uv_stride < d.W ||
+        (long long)d.dst_stride < 3LL * d.W)
+      return fail(c, PC_ERR_ARG, "pc_nv12_to_bgr: bad frame (non-null planes, even 2 <= H, W <= 16384, y_stride >= W, "
+                                 "uv_stride >= W, dst_stride >= 3 W)");
+    Job& j = jobs[i];
+    j.y = d.d_y; j.uv = d.d_uv; j.dst = d.d_dst;
+    j.H = d.H; j.W = d.W; j.y_stride = d.y_stride; j.uv_stride = d.uv_stride; j.dst_stride = d.dst_stride;
+    j.aligned = (((uintptr_t)d.d_y | (uintptr_t)d.d_uv | (uintptr_t)d.d_dst | (uintptr_t)d.y_stride |
+                  (uintptr_t)d.uv_stride | (uintptr_t)d.dst_stride) & 15) == 0;
+    j.ux = (d.W + 15) / 16;
+    if (nwg >= (1LL << 31)) return fail(c, PC_ERR_ARG, "pc_nv12_to_bgr: too many pixels for one launch");
+    j.wg0 = (int32_t)nwg;
+    nwg += ((long long)j.ux * (d.H / 2) + 255) / 256;
+  }
+  if (nwg >= (1LL << 31)) return fail(c, PC_ERR_ARG, "pc_nv12_to_bgr: too many pixels for one launch");
+  void* dj;
+  int rc = stage_copy(c, jobs.data(), sizeof(Job) * (size_t)n, &dj);
+  if (rc) return rc;
+  HIPCHK(c, nv12_to_bgr_launch(dj, n, nwg, c->stream));
+  return PC_OK;
+}
+
+// the frames of a fused downscale: n triples (Y, UV, destination) staged for the kernels
+static int nv12_area_jobs(pc_ctx* c, const char* what, const uint8_t* const* ys, const uint8_t* const* uvs,
+                          uint8_t* const* dsts, int n, int H, int W, int y_stride, int uv_stride,
+                          std::vector<const void*>& jobs) {
+  if (!ys || !uvs || !dsts || n < 0 || n > 65535 || !nv12_size_ok(H, W) || y_stride < W || uv_stride < W)
+    return fail(c, PC_ERR_ARG, std::string(what) + ": bad arguments");
+  jobs.resize(3 * (size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!ys[i] || !uvs[i] || !dsts[i]) return fail(c, PC_ERR_ARG, std::string(what) + ": null frame");
+    jobs[3 * i] = ys[i]; jobs[3 * i + 1] = uvs[i]; jobs[3 * i + 2] = dsts[i];
+  }
+  return PC_OK;
+}
+
+// every coefficient of an INTER_AREA table inside [0, ssize) and every destination's window inside the table
+static bool area_table_ok(const pc_area_tab* t, int n_t, const int32_t* start, int dsize, int ssize) {
+  for (int i = 0; i < n_t; ++i)
+    if (t[i].si < 0 || t[i].si >= ssize) return false;
+  if (start[0] < 0 || start[dsize] > n_t) return false;
+  for (int d = 0; d < dsize; ++d)
+    if (start[d] > start[d + 1]) return false;
+  return true;
+}
+
+extern "C" int pc_nv12_resize_area_batch(pc_ctx* c, const uint8_t* const* ys, const uint8_t* const* uvs,
+                                         uint8_t* const* dsts, int n, int H, int W, int y_stride, int uv_stride,
+                                         const pc_area_tab* xt, const int32_t* xs, int n_x, const pc_area_tab* yt,
+                                         const int32_t* ysr, int n_y, int OH, int OW) {
+  if (!c) return PC_ERR_ARG;
+  std::vector<const void*> jobs;
+  int rc = nv12_area_jobs(c, "pc_nv12_resize_area_batch", ys, uvs, dsts, n, H, W, y_stride, uv_stride, jobs);
+  if (rc) return rc;
+  if (!xt || !xs || !yt || !ysr || n_x <= 0 || n_y <= 0 || OH <= 0 || OW <= 0 || OH > H || OW > W ||
+      !area_table_ok(xt, n_x, xs, OW, W) || !area_table_ok(yt, n_y, ysr, OH, H))
+    return fail(c, PC_ERR_ARG, "pc_nv12_resize_area_batch: bad tables");
+  if (n == 0) return PC_OK;
+  void *dxt, *dxs, *dyt, *dys, *dj;
+  if ((rc = stage_copy(c, xt, sizeof(pc_area_tab) * n_x, &dxt))) return rc;
+  if ((rc = stage_copy(c, xs, sizeof(int32_t) * (OW + 1), &dxs))) return rc;
+  if ((rc = stage_copy(c, yt, sizeof(pc_area_tab) * n_y, &dyt))) return rc;
+  if ((rc = stage_copy(c, ysr, sizeof(int32_t) * (OH + 1), &dys))) return rc;
+  if ((rc = stage_copy(c, jobs.data(), sizeof(void*) * jobs.size(), &dj))) return rc;
+  HIPCHK(c, nv12_resize_area_launch(dj, n, y_stride, uv_stride, (const AreaTab*)dxt, (const int*)dxs,
+                                    (const AreaTab*)dyt, (const int*)dys, OH, OW, c->stream));
+  return PC_OK;
+}
+
+extern "C" int pc_nv12_resize_area_fast_batch(pc_ctx* c, const uint8_t* const* ys, const uint8_t* const* uvs,
+                                              uint8_t* const* dsts, int n, int H, int W, int y_stride, int uv_stride,
+                                              int isx, int isy, int OH, int OW) {
+  if (!c) return PC_ERR_ARG;
+  std::vector<const void*> jobs;
+  int rc = nv12_area_jobs(c, "pc_nv12_resize_area_fast_batch", ys, uvs, dsts, n, H, W, y_stride, uv_stride, jobs);
+  if (rc) return rc;
+  if (isx < 1 || isy < 1 || OH <= 0 || OW <= 0 || (long long)OW * isx > W || (long long)OH * isy > H)
+    return fail(c, PC_ERR_ARG, "pc_nv12_resize_area_fast_batch: bad ratios");
+  if (n == 0) return PC_OK;
+  void* dj;
+  if ((rc = stage_copy(c, jobs.data(), sizeof(void*) * jobs.size(), &dj))) return rc;
+  HIPCHK(c, nv12_resize_area_fast_launch(dj, n, y_stride, uv_stride, isx, isy, OH, OW, c->stream));
   return PC_OK;
 }
 

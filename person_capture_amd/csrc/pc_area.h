@@ -9,26 +9,39 @@ namespace pc {
 
 struct AreaTab { int si; int di; float alpha; };
 
+// A pixel accessor px(sy, sx, v) puts the CN u8 channel values of source pixel (row sy, column sx) into
+// v[CN]: interleaved memory (AreaMemPx), or NV12 planes converted in registers (pc_nv12.hip).
+template <int CN>
+struct AreaMemPx {
+  const uint8_t* __restrict__ src;
+  long long row_stride;
+  __device__ __forceinline__ void operator()(int sy, int sx, int v[CN]) const {
+    const uint8_t* p = src + (long long)sy * row_stride + sx * CN;
+#pragma unroll
+    for (int c = 0; c < CN; ++c) v[c] = p[c];
+  }
+};
+
 // OpenCV's generic (non-integer scale) area path: float weights, accumulated per output pixel in
 // source order (x-window of every source row, then the rows), saturate_cast<uchar> (round half to
 // even) at the end. Window [i0, i1) of the x coefficients, [j0, j1) of the y coefficients; xt(i) /
 // yt(j) return coefficient i / j as an AreaTab (a table in memory, or area_span_tap below).
-template <int CN, typename XT, typename YT>
-__device__ __forceinline__ void area_pixel_taps(const uint8_t* __restrict__ src, long long row_stride, XT xt, int i0,
-                                                int i1, YT yt, int j0, int j1, uint8_t* o) {
+template <int CN, typename PX, typename XT, typename YT>
+__device__ __forceinline__ void area_pixel_taps_px(PX px, XT xt, int i0, int i1, YT yt, int j0, int j1, uint8_t* o) {
   float acc[CN];
 #pragma unroll
   for (int c = 0; c < CN; ++c) acc[c] = 0.f;
   for (int j = j0; j < j1; ++j) {
     const AreaTab ty = yt(j);
-    const uint8_t* row = src + (long long)ty.si * row_stride;
     float rs[CN];
 #pragma unroll
     for (int c = 0; c < CN; ++c) rs[c] = 0.f;
     for (int i = i0; i < i1; ++i) {
       const AreaTab tx = xt(i);
+      int v[CN];
+      px(ty.si, tx.si, v);
 #pragma unroll
-      for (int c = 0; c < CN; ++c) rs[c] += (float)row[tx.si * CN + c] * tx.alpha;
+      for (int c = 0; c < CN; ++c) rs[c] += (float)v[c] * tx.alpha;
     }
 #pragma unroll
     for (int c = 0; c < CN; ++c) acc[c] += rs[c] * ty.alpha;
@@ -38,6 +51,13 @@ __device__ __forceinline__ void area_pixel_taps(const uint8_t* __restrict__ src,
     int v = __float2int_rn(acc[c]);
     o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
   }
+}
+
+// The same over interleaved u8 memory.
+template <int CN, typename XT, typename YT>
+__device__ __forceinline__ void area_pixel_taps(const uint8_t* __restrict__ src, long long row_stride, XT xt, int i0,
+                                                int i1, YT yt, int j0, int j1, uint8_t* o) {
+  area_pixel_taps_px<CN>(AreaMemPx<CN>{src, row_stride}, xt, i0, i1, yt, j0, j1, o);
 }
 
 // The same with the coefficients in tables built on the host (imageops.area_tables).
@@ -87,20 +107,32 @@ __device__ __forceinline__ AreaTab area_span_tap(const AreaSpan& s, int d, int t
 // An exact integer ratio isx x isy (hal::resize "is_area_fast", resizeAreaFast_Invoker): 2x2 takes
 // ResizeAreaFastVec ((sum + 2) >> 2 for every byte); other ratios
 // saturate_cast<uchar>(sum * (1.f / area)) (round half to even).
+// (the sums are integers, so the channels of a pixel are summed together: one accessor call per tap)
+template <int CN, typename PX>
+__device__ __forceinline__ void area_fast_pixel_px(PX px, int isx, int isy, int dx, int dy, uint8_t* o) {
+  const float scale = 1.f / (float)(isx * isy);
+  int sum[CN];
+#pragma unroll
+  for (int c = 0; c < CN; ++c) sum[c] = 0;
+  for (int j = 0; j < isy; ++j) {
+    for (int i = 0; i < isx; ++i) {
+      int v[CN];
+      px(dy * isy + j, dx * isx + i, v);
+#pragma unroll
+      for (int c = 0; c < CN; ++c) sum[c] += v[c];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CN; ++c) {
+    int v = (isx == 2 && isy == 2) ? ((sum[c] + 2) >> 2) : __float2int_rn((float)sum[c] * scale);
+    o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+  }
+}
+
 template <int CN>
 __device__ __forceinline__ void area_fast_pixel(const uint8_t* __restrict__ src, long long row_stride, int isx,
                                                 int isy, int dx, int dy, uint8_t* o) {
-  const float scale = 1.f / (float)(isx * isy);
-#pragma unroll
-  for (int c = 0; c < CN; ++c) {
-    int sum = 0;
-    for (int j = 0; j < isy; ++j) {
-      const uint8_t* row = src + (long long)(dy * isy + j) * row_stride + (dx * isx) * CN + c;
-      for (int i = 0; i < isx; ++i) sum += row[i * CN];
-    }
-    int v = (isx == 2 && isy == 2) ? ((sum + 2) >> 2) : __float2int_rn((float)sum * scale);
-    o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-  }
+  area_fast_pixel_px<CN>(AreaMemPx<CN>{src, row_stride}, isx, isy, dx, dy, o);
 }
 
 }  // namespace pc

@@ -21,6 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import frames as frames_mod
 from . import models_yolo
 from ._lib import PC_PREC_F16, PC_PREC_F32, YoloLetterboxDesc, YoloScale, check
 from .engines import opencv_vresize_simd_end
@@ -126,7 +127,9 @@ class PersonDetector:
         return [{"xyxy": [float(v) for v in d[:4]], "conf": float(d[4]), "cls": 0} for d in dets]
 
     def detect_batch(self, frames: Sequence[np.ndarray], conf: float = 0.35, iou: float = 0.45) -> List[List[dict]]:
-        """Batched detect(): frames grouped by letterbox canvas, one device call per group."""
+        """Batched detect(): frames grouped by letterbox canvas, one device call per group. A frame may
+        be a frames.Nv12Frame: it is uploaded as NV12 and converted on the device (pc_nv12_to_bgr, one
+        launch for the NV12 frames of a group)."""
         out: List[List[dict]] = [[] for _ in frames]
         groups: Dict[Tuple[int, int], List[int]] = {}
         for i, f in enumerate(frames):
@@ -139,12 +142,22 @@ class PersonDetector:
             eng = self._engine(Hp, Wp)
             for s in range(0, len(idx), eng.max_batch):
                 part = idx[s:s + eng.max_batch]
-                bufs, devs = [], []
+                devs, nv12 = [], []
                 for i in part:
+                    if isinstance(frames[i], frames_mod.Nv12Frame):
+                        f = frames[i]
+                        d = self._ctx.scratch(f"yolo_frame{len(devs)}", f.H * f.W * 3)
+                        if not f.is_device:
+                            f = frames_mod.stage_nv12(self._ctx, f, self._ctx.scratch(f"yolo_frame{len(devs)}_nv12",
+                                                                                      f.packed_bytes).ptr)
+                        nv12.append(f.job(d.ptr))
+                        devs.append((d.ptr, f.H, f.W, f.W * 3))
+                        continue
                     f = np.ascontiguousarray(frames[i], dtype=np.uint8)
                     d = self._ctx.scratch(f"yolo_frame{len(devs)}", f.nbytes)
                     self._ctx.upload(f, d)
                     devs.append((d.ptr, f.shape[0], f.shape[1], f.strides[0]))
+                frames_mod.convert_on_device(self._ctx, nv12)
                 res = eng.read(eng.detect_device(devs, conf, iou), len(part))
                 for i, r in zip(part, res):
                     out[i] = self._to_dicts(r)

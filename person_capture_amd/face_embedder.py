@@ -42,7 +42,9 @@ use_arcface=False (the curator without a reference image, dataset_curator.py:329
 f16 / f16x3 and PERSON_CAPTURE_AMD_FACE_CLIP_BATCH its arithmetic and batch) With the
 YOLOv8-face backend use_arcface=False raises RuntimeError at construction, as the reference does for
 unavailable backends. Host frames reach the device through the native pinned staging ring
-(pc_frame_stage) on a copy stream.
+(pc_frame_stage) on a copy stream. A frame may also be a frames.Nv12Frame (the reference's NV12 pipe
+format, video_io.py:2888-2912): it is staged as NV12, half the bytes, and converted on the device
+(pc_nv12_to_bgr) into the buffer a BGR frame would have been copied to.
 """
 from __future__ import annotations
 
@@ -54,6 +56,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import frames as frames_mod
 from . import imageops, models, models_clip, onnx_models
 from ._lib import (CHIP_BYTES, PC_PREC_F16, PC_PREC_F16C8, PC_PREC_F16X3, PC_PREC_F32, ChipDesc, ResizeDesc, WarpDesc,
                    check)
@@ -259,6 +262,39 @@ def dev_resize_batch(ctx: GpuContext, imgs: Sequence[_DevImage], keys: Sequence[
         for i, b in zip(idx, bufs):
             out[i] = _DevImage(b.ptr, nh, nw, nw * 3, b)
     return out
+
+
+def dev_nv12_resize_batch(ctx: GpuContext, frames: Sequence["frames_mod.Nv12Frame"], keys: Sequence[str],
+                          dsize: Tuple[int, int]) -> List[_DevImage]:
+    """cv2.resize(nv12_to_bgr(frame), dsize, INTER_AREA) for device NV12 frames of one geometry (size and
+    plane strides): where both axes shrink, the fused conversion + INTER_AREA kernels
+    (pc_nv12_resize_area_batch / pc_nv12_resize_area_fast_batch, one launch, no full-size BGR frame);
+    any other cv::resize path converts first (pc_nv12_to_bgr) and takes dev_resize. Same bytes."""
+    f0 = frames[0]
+    H, W, ys, uvs = f0.H, f0.W, f0.y_stride, f0.uv_stride
+    if any((f.H, f.W, f.y_stride, f.uv_stride) != (H, W, ys, uvs) or not f.is_device for f in frames):
+        raise ValueError("dev_nv12_resize_batch: device NV12 frames of one geometry")
+    p = imageops.resize_plan(H, W, dsize, 0.0, 0.0, True)
+    nw, nh, n = p["new_w"], p["new_h"], len(frames)
+    if p["kind"] not in ("area", "area_fast"):
+        out = []
+        for f, key in zip(frames, keys):
+            full = ctx.scratch(key + "_full", H * W * 3)
+            frames_mod.convert_on_device(ctx, [f.job(full.ptr)])
+            out.append(dev_resize(ctx, _DevImage(full.ptr, H, W, W * 3, full), key, dsize, area=True))
+        return out
+    bufs = [ctx.scratch(key, nw * nh * 3) for key in keys]
+    yp = (C.c_void_p * n)(*[f.y_ptr for f in frames])
+    uvp = (C.c_void_p * n)(*[f.uv_ptr for f in frames])
+    dsts = (C.c_void_p * n)(*[b.ptr for b in bufs])
+    if p["kind"] == "area":
+        (xt, xs), (yt, ysr) = imageops.area_tables(W, nw, p["scale_x"]), imageops.area_tables(H, nh, p["scale_y"])
+        check(ctx.lib.pc_nv12_resize_area_batch(ctx.handle, yp, uvp, dsts, n, H, W, ys, uvs, xt, xs, len(xt), yt, ysr,
+                                                len(yt), nh, nw), ctx.handle, "nv12_resize_area_batch")
+    else:
+        check(ctx.lib.pc_nv12_resize_area_fast_batch(ctx.handle, yp, uvp, dsts, n, H, W, ys, uvs, p["isx"], p["isy"],
+                                                     nh, nw), ctx.handle, "nv12_resize_area_fast_batch")
+    return [_DevImage(b.ptr, nh, nw, nw * 3, b) for b in bufs]
 
 
 class FaceEmbedder(YoloFaceBranch):
@@ -528,7 +564,38 @@ class FaceEmbedder(YoloFaceBranch):
             self._scrfd_engines[D] = e
         return e
 
+    def _stage_nv12(self, entries: Sequence[Tuple["frames_mod.Nv12Frame", int, str]]) -> None:
+        """NV12 frames -> BGR at their destinations: entries of (frame, destination pointer, scratch key of
+        the frame's NV12 bytes). Host frames are staged on the copy stream (pc_frame_stage, W bytes x 3 H / 2
+        rows); the detection stream waits for them and converts every frame in ONE pc_nv12_to_bgr."""
+        jobs, staged = [], False
+        for f, d_dst, key in entries:
+            dev = f
+            if not f.is_device:
+                dev = frames_mod.stage_nv12(self._h2d, f, self._ctx.scratch(key, f.packed_bytes).ptr,
+                                            self._stage_threads)
+                staged = True
+            jobs.append(dev.job(d_dst))
+        if staged:
+            self._ctx.wait_fence(self._h2d.fence("h2d_nv12"))
+        frames_mod.convert_on_device(self._ctx, jobs)
+
+    def _upload_nv12_planes(self, f: "frames_mod.Nv12Frame", key: str) -> "frames_mod.Nv12Frame":
+        """A host NV12 frame staged as it is (no conversion): its device form, ordered before later work
+        of the detection stream."""
+        if f.is_device:
+            return f
+        buf = self._ctx.scratch(key, f.packed_bytes)
+        dev = frames_mod.stage_nv12(self._h2d, f, buf.ptr, self._stage_threads)
+        self._ctx.wait_fence(self._h2d.fence("h2d_up"))
+        dev._buf = buf
+        return dev
+
     def _upload(self, bgr: np.ndarray, key: str = "frame") -> _DevImage:
+        if isinstance(bgr, frames_mod.Nv12Frame):
+            buf = self._ctx.scratch(key, bgr.H * bgr.W * 3)
+            self._stage_nv12([(bgr, buf.ptr, key + "_nv12")])
+            return _DevImage(buf.ptr, bgr.H, bgr.W, bgr.W * 3, buf)
         a = np.asarray(bgr)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("expected an HxWx3 BGR uint8 image")
@@ -806,8 +873,14 @@ class FaceEmbedder(YoloFaceBranch):
             if dev_frames is not None:
                 ims = list(dev_frames)
             else:
-                ims = [None if f is None or f.size == 0 else self._upload(f, key=f"yf_frame{i}")
-                       for i, f in enumerate(frames)]
+                ims = [None if f is None or f.size == 0 or isinstance(f, frames_mod.Nv12Frame)
+                       else self._upload(f, key=f"yf_frame{i}") for i, f in enumerate(frames)]
+                nv = [(i, f) for i, f in enumerate(frames) if isinstance(f, frames_mod.Nv12Frame)]
+                if nv:   # every NV12 frame of the call in one conversion
+                    bufs = [self._ctx.scratch(f"yf_frame{i}", f.H * f.W * 3) for i, f in nv]
+                    self._stage_nv12([(f, b.ptr, f"yf_frame{i}_nv12") for (i, f), b in zip(nv, bufs)])
+                    for (i, f), b in zip(nv, bufs):
+                        ims[i] = _DevImage(b.ptr, f.H, f.W, f.W * 3, b)
             return self._extract_batch_yolo(ims, imgsz)
         imgs: List[Optional[_DevImage]] = []
         host_src: Dict[int, np.ndarray] = {}   # host frames not yet staged (device buffers reserved)
@@ -853,9 +926,19 @@ class FaceEmbedder(YoloFaceBranch):
             if staged:
                 # host frames of this chunk: pinned staging + H2D on the copy stream, which the
                 # detection stream waits on; the copies of chunk c+1 overlap chunk c's detection
+                nv12 = []   # conversion jobs, run behind the chunk's H2D fence
                 for i in staged:
-                    self._h2d.stage_frame(host_src.pop(i), imgs[i].ptr, self._stage_threads)
+                    f = host_src.pop(i)
+                    if isinstance(f, frames_mod.Nv12Frame):
+                        if not f.is_device:
+                            f = frames_mod.stage_nv12(self._h2d, f, self._ctx.scratch(f"frame{i}_nv12",
+                                                                                      f.packed_bytes).ptr,
+                                                      self._stage_threads)
+                        nv12.append(f.job(imgs[i].ptr))
+                    else:
+                        self._h2d.stage_frame(f, imgs[i].ptr, self._stage_threads)
                 self._ctx.wait_fence(self._h2d.fence(f"h2d{ci % 4}"))
+                frames_mod.convert_on_device(self._ctx, nv12)
             by_dyn: Dict[int, List[int]] = {}
             for i in chunks[ci]:
                 if spec_dyn[i] is not None:

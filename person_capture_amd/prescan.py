@@ -21,6 +21,12 @@ chunk is cut there: the FaceEmbedder's per-frame policy state is restored from i
 trace and the next chunk starts at that sample. Results are therefore identical to the
 sequential loop; a regime change only costs the tail of one chunk.
 
+A sample may arrive as a frames.Nv12Frame (the reference's NV12 pipe format, video_io.py:2888-2912):
+it is uploaded as NV12 and converted on the device. With PERSON_CAPTURE_AMD_NV12_FUSED=1 a sample wider
+than `prescan_max_width` goes through the fused conversion + INTER_AREA downscale
+(pc_nv12_resize_area_batch) instead, and its full-size BGR frame is never written; the bytes are the
+same either way (DESIGN.md §12 has the measurement behind the default).
+
 Not here (GUI/IO plumbing outside the per-frame hot path): the command queue (pause, seek,
 step, live cfg edits), decoder seeking, previews and progress signals, and the edge
 refinement re-scan (:1670-) which reuses this same per-sample step at a finer stride.
@@ -33,6 +39,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .frames import Nv12Frame
 from .match import fd_min, stream_ref_bank_update
 
 
@@ -133,6 +140,9 @@ class PrescanRunner:
         self.cuts = 0
         self.spec: Optional[List[SpecRecord]] = None   # run(..., speculate=True) fills it
         self.initial_state: Optional[tuple] = None
+        # NV12 samples wider than prescan_max_width: fused conversion + downscale (off: convert, then the
+        # BGR path's downscale)
+        self.nv12_fused = os.getenv("PERSON_CAPTURE_AMD_NV12_FUSED", "0") == "1"
 
     def samples(self) -> List[int]:
         """Frame index of every sample position (gui_app.py:1468: range(0, total, stride))."""
@@ -154,10 +164,8 @@ class PrescanRunner:
         f.set_policy_state(state)
         f._prescan_rr_mode = "full" if active else "rr"
         f.set_prescan_hint(escalate=active)
-        im = frame_at(self.samples()[pos])
-        if not hasattr(im, "ptr"):
-            im = f._upload(np.ascontiguousarray(im), key="prescan_src0")
-        im = self._downscale(im, 0)
+        im = self._to_device(frame_at(self.samples()[pos]), "prescan_src0")
+        im = self._downscale_many([im], [0])[0] if isinstance(im, Nv12Frame) else self._downscale(im, 0)
         res = f.extract_batch([None], dev_frames=[im])
         return res[0], f.policy_state()
 
@@ -183,10 +191,7 @@ class PrescanRunner:
         todo = [j for j, skip in plan if not skip]
         srcs = []
         for j in todo:
-            im = frame_at(samples[j])
-            if not hasattr(im, "ptr"):
-                im = f._upload(np.ascontiguousarray(im), key=f"prescan_src{j % self.batch}")
-            srcs.append(im)
+            srcs.append(self._to_device(frame_at(samples[j]), f"prescan_src{j % self.batch}"))
         ims = self._downscale_many(srcs, [j - k for j in todo])
         state0 = f.policy_state()
         f.state_trace = []
@@ -250,19 +255,34 @@ class PrescanRunner:
                 return (st.fd9_streak % period) != 0, True
         return False, False
 
+    def _to_device(self, im, key: str):
+        """What frame_at returned, on the device: a _DevImage as it is, a host BGR array uploaded, an NV12
+        frame converted to BGR - or, for the fused downscale, kept as NV12 planes."""
+        if hasattr(im, "ptr"):
+            return im
+        if isinstance(im, Nv12Frame):
+            if self.nv12_fused and im.W > int(self.cfg.prescan_max_width):
+                return self.face._upload_nv12_planes(im, key + "_nv12")
+            return self.face._upload(im, key=key)
+        return self.face._upload(np.ascontiguousarray(im), key=key)
+
     def _downscale_many(self, ims, ks):
         """_downscale of a chunk's samples: the frames wider than prescan_max_width in one batched
-        INTER_AREA launch (face_embedder.dev_resize_batch), the same bytes as one resize each."""
-        from .face_embedder import dev_resize_batch
+        INTER_AREA launch (face_embedder.dev_resize_batch), the same bytes as one resize each. NV12 planes
+        (_to_device, fused mode) take the fused kernels, one launch per source geometry."""
+        from .face_embedder import dev_nv12_resize_batch, dev_resize_batch
         Wmax = int(self.cfg.prescan_max_width)
         out = list(ims)
         wide = [t for t, im in enumerate(ims) if im.W > Wmax]
         by_dims = {}
         for t in wide:
-            by_dims.setdefault((ims[t].H, ims[t].W), []).append(t)
-        for (H, W), ts in by_dims.items():
+            im = ims[t]
+            planes = (im.y_stride, im.uv_stride) if isinstance(im, Nv12Frame) else None
+            by_dims.setdefault((im.H, im.W, planes), []).append(t)
+        for (H, W, planes), ts in by_dims.items():
             nh = int(round(H * (Wmax / float(W))))
-            res = dev_resize_batch(self.face._ctx, [ims[t] for t in ts], [f"prescan{ks[t]}" for t in ts], (Wmax, nh))
+            resize = dev_resize_batch if planes is None else dev_nv12_resize_batch
+            res = resize(self.face._ctx, [ims[t] for t in ts], [f"prescan{ks[t]}" for t in ts], (Wmax, nh))
             for t, r in zip(ts, res):
                 out[t] = r
         return out
