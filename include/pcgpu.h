@@ -40,6 +40,9 @@
  *                                      the NV12 pipe format (PC_PIPE_PIXFMT=nv12, video_io.py:1225-1228, 1901-1904)
  *   pc_nv12_resize_area_batch /        the same conversion followed by the pre-scan's cv2.resize(..., INTER_AREA)
  *   pc_nv12_resize_area_fast_batch     (gui_app.py:1505-1507) in one pass, no full-size BGR frame in between
+ *   pc_hdr_to_bgr                      the float32 HDR pipe format (gbrpf32le, video_io.py:2513-2520): _eotf_pq /
+ *                                      _eotf_hlg (video_io.py:3015-3018, 3239-3258) + _python_tonemap_to_bgr8
+ *                                      (video_io.py:3183-3192, 3276-3291) with _hable_filmic and _oetf_bt709
  *   pc_yolo_detect                     PersonDetector.detect -> [ext] ultralytics YOLO.predict(conf, iou=0.45,
  *                                      classes=[0], max_det=40, imgsz=640) (detectors.py:271-296)
  *   pc_yolo_pose_detect                FaceEmbedder YOLOv8-face backend (Y8F_DEFAULT, face_embedder.py:33) ->
@@ -185,6 +188,27 @@ typedef struct pc_nv12_desc {
   int32_t pad_;
 } pc_nv12_desc;
 #define PC_NV12_MAX_SIDE 16384
+
+/* One HDR frame of pc_hdr_to_bgr on the device: float32 R, G and B samples of the PQ / HLG signal (or of
+ * linear light), sample (y, x) of a channel at its pointer + y * row_stride + x * pix_stride floats, and the
+ * BGR u8 destination (H rows of 3 W bytes, dst_stride apart). pix_stride 1: three planes (the pipe's gbrpf32le
+ * bytes wrapped as they are: d_g, d_b, d_r in that order in memory); pix_stride 3: an interleaved H x W x 3
+ * RGB array (d_g = d_r + 1, d_b = d_r + 2). H and W 1 .. PC_HDR_MAX_SIDE, no parity requirement.
+ * target_nits / peak_nits: the arguments of _python_tonemap_to_bgr8. */
+typedef struct pc_hdr_desc {
+  const float* d_r;
+  const float* d_g;
+  const float* d_b;
+  int32_t H, W, pix_stride, row_stride;
+  uint8_t* d_dst;
+  int32_t dst_stride;
+  int32_t transfer; /* PC_HDR_PQ / PC_HDR_HLG / PC_HDR_LINEAR */
+  double target_nits, peak_nits;
+} pc_hdr_desc;
+#define PC_HDR_MAX_SIDE 16384
+#define PC_HDR_PQ 0     /* _eotf_pq (video_io.py:3239-3251) */
+#define PC_HDR_HLG 1    /* _eotf_hlg (video_io.py:3254-3258), the reader's _transfer == "arib-std-b67" */
+#define PC_HDR_LINEAR 2 /* the samples are linear light already (1.0 = 10 000 nits) */
 
 /* One crop of the dataset curator's metrics batch (pc_crop_metrics): a BGR u8 image on the device and
  * the geometry of its two INTER_AREA targets, [0] the <= 256 plane of sharpness_norm (w2 x h2;
@@ -374,6 +398,20 @@ int pc_nv12_resize_area_batch(pc_ctx* ctx, const uint8_t* const* h_ys, const uin
 int pc_nv12_resize_area_fast_batch(pc_ctx* ctx, const uint8_t* const* h_ys, const uint8_t* const* h_uvs,
                                    uint8_t* const* h_dsts, int n, int H, int W, int y_stride, int uv_stride, int isx,
                                    int isy, int OH, int OW);
+/* _eotf_pq / _eotf_hlg (video_io.py:3239-3258) followed by _python_tonemap_to_bgr8 (video_io.py:3276-3291)
+ * for n HDR frames of any mix of sizes, layouts and transfers in one launch: per pixel the EOTF of each
+ * channel, BT.2020 luminance, the Hable curve, the rescale, the BT.709 OETF, trunc(o * 255 + 0.5), stored
+ * B, G, R. Every operation in f32 rounded once in the reference's order (no fused multiply-add, IEEE
+ * division, subnormals kept); power and exp are the f64 functions rounded to f32 (the operation in full:
+ * person_capture_amd/frames_hdr.py). Frames whose sample pointers and row strides are multiples of 16 bytes
+ * and whose destination pointer and stride are multiples of 4 move 16 bytes per load and 12 per store;
+ * others (and the last W % 4 pixels of a row) go float by float and byte by byte. No float outside the W
+ * pixels of a source row is read, nothing outside [row, row + 3 W) of a destination row written; a NaN
+ * sample gives some byte. n == 0: PC_OK, nothing enqueued. A null pointer, a sample pointer not 4-byte
+ * aligned, H or W outside [1, PC_HDR_MAX_SIDE], pix_stride other than 1 or 3, row_stride < W pix_stride,
+ * dst_stride < 3 W, an unknown transfer, target_nits or peak_nits non-finite or <= 0, or n < 0: PC_ERR_ARG
+ * before anything is staged or enqueued, whichever frame of the batch is the bad one. */
+int pc_hdr_to_bgr(pc_ctx* ctx, const pc_hdr_desc* h_descs, int n);
 
 /* ---- detection ---- */
 /* Runs letterbox -> SCRFD net -> decode(score >= det_thresh) -> NMS(nms_thresh) for n frames.

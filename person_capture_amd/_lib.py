@@ -86,6 +86,19 @@ class Nv12Desc(C.Structure):
 assert C.sizeof(Nv12Desc) == 48
 PC_NV12_MAX_SIDE = 16384
 
+
+class HdrDesc(C.Structure):
+    _fields_ = [("d_r", C.c_void_p), ("d_g", C.c_void_p), ("d_b", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
+                ("pix_stride", C.c_int32), ("row_stride", C.c_int32), ("d_dst", C.c_void_p),
+                ("dst_stride", C.c_int32), ("transfer", C.c_int32), ("target_nits", C.c_double),
+                ("peak_nits", C.c_double)]
+
+
+assert C.sizeof(HdrDesc) == 72
+PC_HDR_MAX_SIDE = 16384
+PC_HDR_PQ, PC_HDR_HLG, PC_HDR_LINEAR = 0, 1, 2
+PC_HDR_TRANSFERS = {"pq": PC_HDR_PQ, "hlg": PC_HDR_HLG, "linear": PC_HDR_LINEAR}
+
 PC_CHIP_COPY, PC_CHIP_AREA_FAST, PC_CHIP_AREA, PC_CHIP_LINEAR = 0, 1, 2, 3
 CHIP_KINDS = {PC_CHIP_COPY: "copy", PC_CHIP_AREA_FAST: "area_fast", PC_CHIP_AREA: "area", PC_CHIP_LINEAR: "linear"}
 CHIP_BYTES = 112 * 112 * 3
@@ -168,6 +181,7 @@ SIGNATURES = {
     "pc_nv12_resize_area_batch": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(AreaTab), C.POINTER(C.c_int32), _I,
                                    C.POINTER(AreaTab), C.POINTER(C.c_int32), _I, _I, _I], _I),
     "pc_nv12_resize_area_fast_batch": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I], _I),
+    "pc_hdr_to_bgr": ([_P, C.POINTER(HdrDesc), _I], _I),
     "pc_scrfd_detect": ([_P, C.POINTER(LetterboxDesc), _I, _I, _F, _F, C.POINTER(_F), _I, _P, _P, _P, _P], _I),
     "pc_embed_finalize": ([_P, _P, _I, _I, _I, _I, _P], _I),
     "pc_arcface_embed": ([_P, _P, _I, _I, _P], _I),

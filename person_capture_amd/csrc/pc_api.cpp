@@ -48,6 +48,8 @@ hipError_t nv12_resize_area_launch(const void* d_jobs, int n, int y_stride, int 
                                    hipStream_t s);
 hipError_t nv12_resize_area_fast_launch(const void* d_jobs, int n, int y_stride, int uv_stride, int isx, int isy,
                                         int OH, int OW, hipStream_t s);
+// pc_hdr.hip
+hipError_t hdr_to_bgr_launch(const void* d_jobs, int n, long long nwg, hipStream_t s);
 hipError_t curate_metrics_launch(const void* d_imgs, int n, const void* d_bands, int nbands, const void* d_tabs,
                                  const int* d_starts, const double* d_dct, int max_pixels, hipStream_t s);
 hipError_t sim_matrix_launch(const float* F, int n, int dim, float* S, hipStream_t s);
@@ -113,6 +115,7 @@ static_assert(sizeof(pc_curate_desc) == 72 && sizeof(pc_curate_record) == 1312, 
 static_assert(sizeof(pc_resize_desc) == 80, "resize desc layout");
 static_assert(sizeof(pc_chip_desc) == 24, "chip desc layout");
 static_assert(sizeof(pc_nv12_desc) == 48, "nv12 desc layout");
+static_assert(sizeof(pc_hdr_desc) == 72, "hdr desc layout");
 static_assert(sizeof(pc_yolo_letterbox_desc) == 64, "yolo letterbox desc layout");
 static_assert(sizeof(pc_yolo_scale) == 20, "yolo scale layout");
 
@@ -713,6 +716,56 @@ extern "C" int pc_nv12_to_bgr(pc_ctx* c, const pc_nv12_desc* h, int n) {
   int rc = stage_copy(c, jobs.data(), sizeof(Job) * (size_t)n, &dj);
   if (rc) return rc;
   HIPCHK(c, nv12_to_bgr_launch(dj, n, nwg, c->stream));
+  return PC_OK;
+}
+
+// ---- HDR linear-light frames (pc_hdr.hip) ----
+extern "C" int pc_hdr_to_bgr(pc_ctx* c, const pc_hdr_desc* h, int n) {
+  if (!c) return PC_ERR_ARG;
+  if (n < 0 || (n > 0 && !h)) return fail(c, PC_ERR_ARG, "pc_hdr_to_bgr: bad arguments");
+  if (n == 0) return PC_OK;
+  struct Job {   // pc_hdr.hip HdrJob
+    const float *r, *g, *b; uint8_t* dst;
+    int32_t H, W, pix_stride, row_stride, dst_stride, transfer;
+    float t32, peak;
+    int32_t wide, ux, wg0, pad_;
+  };
+  static_assert(sizeof(Job) == 80, "hdr job layout");
+  std::vector<Job> jobs((size_t)n);
+  long long nwg = 0;
+  for (int i = 0; i < n; ++i) {
+    const pc_hdr_desc& d = h[i];
+    const uintptr_t src = (uintptr_t)d.d_r | (uintptr_t)d.d_g | (uintptr_t)d.d_b;
+    if (!d.d_r || !d.d_g || !d.d_b || !d.d_dst || (src & 3) || d.H < 1 || d.W < 1 || d.H > PC_HDR_MAX_SIDE ||
+        d.W > PC_HDR_MAX_SIDE || (d.pix_stride != 1 && d.pix_stride != 3) ||
+        (long long)d.row_stride < (long long)d.W * d.pix_stride || (long long)d.dst_stride < 3LL * d.W ||
+        d.transfer < PC_HDR_PQ || d.transfer > PC_HDR_LINEAR || !std::isfinite(d.target_nits) ||
+        !std::isfinite(d.peak_nits) || d.target_nits <= 0 || d.peak_nits <= 0)
+      return fail(c, PC_ERR_ARG, "pc_hdr_to_bgr: bad frame (non-null 4-byte aligned samples, 1 <= H, W <= 16384, "
+                                 "pix_stride 1 or 3, row_stride >= W pix_stride, dst_stride >= 3 W, a known "
+                                 "transfer, finite target_nits and peak_nits > 0)");
+    Job& j = jobs[i];
+    memset(&j, 0, sizeof(j));
+    j.r = d.d_r; j.g = d.d_g; j.b = d.d_b; j.dst = d.d_dst;
+    j.H = d.H; j.W = d.W; j.pix_stride = d.pix_stride; j.row_stride = d.row_stride; j.dst_stride = d.dst_stride;
+    j.transfer = d.transfer;
+    j.t32 = (float)d.target_nits;
+    j.peak = (float)std::max(d.peak_nits, 1e-3);
+    // 16-byte loads: planes each aligned, or one interleaved R, G, B triple sequence from an aligned d_r
+    const bool src16 = d.pix_stride == 1 ? (src & 15) == 0
+                                         : (((uintptr_t)d.d_r & 15) == 0 && d.d_g == d.d_r + 1 && d.d_b == d.d_r + 2);
+    j.wide = src16 && (((size_t)d.row_stride * 4) & 15) == 0 &&
+             (((uintptr_t)d.d_dst | (uintptr_t)d.dst_stride) & 3) == 0;
+    j.ux = (d.W + 3) / 4;
+    if (nwg >= (1LL << 31)) return fail(c, PC_ERR_ARG, "pc_hdr_to_bgr: too many pixels for one launch");
+    j.wg0 = (int32_t)nwg;
+    nwg += ((long long)j.ux * d.H + 255) / 256;
+  }
+  if (nwg >= (1LL << 31)) return fail(c, PC_ERR_ARG, "pc_hdr_to_bgr: too many pixels for one launch");
+  void* dj;
+  int rc = stage_copy(c, jobs.data(), sizeof(Job) * (size_t)n, &dj);
+  if (rc) return rc;
+  HIPCHK(c, hdr_to_bgr_launch(dj, n, nwg, c->stream));
   return PC_OK;
 }
 

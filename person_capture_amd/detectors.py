@@ -22,6 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import frames as frames_mod
+from . import frames_hdr
 from . import models_yolo
 from ._lib import PC_PREC_F16, PC_PREC_F32, YoloLetterboxDesc, YoloScale, check
 from .engines import opencv_vresize_simd_end
@@ -107,6 +108,7 @@ class PersonDetector:
         self.precision = _precision()
         from .face_embedder import get_context
         self._ctx = get_context(self._device_index)
+        self._hdr = frames_hdr.HdrStager.shared(self._ctx, key="yolo_hdr_src")
         seed = int(os.getenv("PERSON_CAPTURE_AMD_SEED", "0"))
         if callable(progress):
             progress(f"pcgpu: synthetic weights for yolov8{self.scale} (no checkpoint offline)")
@@ -129,7 +131,8 @@ class PersonDetector:
     def detect_batch(self, frames: Sequence[np.ndarray], conf: float = 0.35, iou: float = 0.45) -> List[List[dict]]:
         """Batched detect(): frames grouped by letterbox canvas, one device call per group. A frame may
         be a frames.Nv12Frame: it is uploaded as NV12 and converted on the device (pc_nv12_to_bgr, one
-        launch for the NV12 frames of a group)."""
+        launch for the NV12 frames of a group), or a frames_hdr.HdrFrame: its floats go through two source
+        scratch buffers and pc_hdr_to_bgr converts them into the frame's BGR buffer."""
         out: List[List[dict]] = [[] for _ in frames]
         groups: Dict[Tuple[int, int], List[int]] = {}
         for i, f in enumerate(frames):
@@ -151,6 +154,12 @@ class PersonDetector:
                             f = frames_mod.stage_nv12(self._ctx, f, self._ctx.scratch(f"yolo_frame{len(devs)}_nv12",
                                                                                       f.packed_bytes).ptr)
                         nv12.append(f.job(d.ptr))
+                        devs.append((d.ptr, f.H, f.W, f.W * 3))
+                        continue
+                    if isinstance(frames[i], frames_hdr.HdrFrame):
+                        f = frames[i]
+                        d = self._ctx.scratch(f"yolo_frame{len(devs)}", f.H * f.W * 3)
+                        self._hdr.convert([(f, d.ptr)])
                         devs.append((d.ptr, f.H, f.W, f.W * 3))
                         continue
                     f = np.ascontiguousarray(frames[i], dtype=np.uint8)

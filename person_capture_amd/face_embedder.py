@@ -44,7 +44,9 @@ YOLOv8-face backend use_arcface=False raises RuntimeError at construction, as th
 unavailable backends. Host frames reach the device through the native pinned staging ring
 (pc_frame_stage) on a copy stream. A frame may also be a frames.Nv12Frame (the reference's NV12 pipe
 format, video_io.py:2888-2912): it is staged as NV12, half the bytes, and converted on the device
-(pc_nv12_to_bgr) into the buffer a BGR frame would have been copied to.
+(pc_nv12_to_bgr) into the buffer a BGR frame would have been copied to. Or a frames_hdr.HdrFrame (the float32
+HDR pipe format, video_io.py:3005-3018, 3276-3291): its floats, 4 x the BGR bytes, go through two source
+scratch buffers whatever the batch (frames_hdr.HdrStager) and pc_hdr_to_bgr converts them into that buffer.
 """
 from __future__ import annotations
 
@@ -57,6 +59,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import frames as frames_mod
+from . import frames_hdr
 from . import imageops, models, models_clip, onnx_models
 from ._lib import (CHIP_BYTES, PC_PREC_F16, PC_PREC_F16C8, PC_PREC_F16X3, PC_PREC_F32, ChipDesc, ResizeDesc, WarpDesc,
                    check)
@@ -432,6 +435,7 @@ class FaceEmbedder(YoloFaceBranch):
         # native pinned staging ring on a copy stream of their own (pc_frame_stage)
         self._h2d = get_context(self._device_index, "h2d")
         self._stage_threads = int(os.getenv("PERSON_CAPTURE_AMD_STAGE_THREADS", "8"))
+        self._hdr = frames_hdr.HdrStager.shared(self._ctx, self._h2d, self._stage_threads)
         self._graph_batch = int(os.getenv("PERSON_CAPTURE_AMD_GRAPH_BATCH", "128"))
         self._arc = self._clip = None
         if not self.use_arcface:
@@ -595,6 +599,10 @@ class FaceEmbedder(YoloFaceBranch):
         if isinstance(bgr, frames_mod.Nv12Frame):
             buf = self._ctx.scratch(key, bgr.H * bgr.W * 3)
             self._stage_nv12([(bgr, buf.ptr, key + "_nv12")])
+            return _DevImage(buf.ptr, bgr.H, bgr.W, bgr.W * 3, buf)
+        if isinstance(bgr, frames_hdr.HdrFrame):
+            buf = self._ctx.scratch(key, bgr.H * bgr.W * 3)
+            self._hdr.convert([(bgr, buf.ptr)])
             return _DevImage(buf.ptr, bgr.H, bgr.W, bgr.W * 3, buf)
         a = np.asarray(bgr)
         if a.ndim != 3 or a.shape[2] != 3:
@@ -927,9 +935,12 @@ class FaceEmbedder(YoloFaceBranch):
                 # host frames of this chunk: pinned staging + H2D on the copy stream, which the
                 # detection stream waits on; the copies of chunk c+1 overlap chunk c's detection
                 nv12 = []   # conversion jobs, run behind the chunk's H2D fence
+                hdr = []    # HDR frames: staged and converted one by one through two source scratch buffers
                 for i in staged:
                     f = host_src.pop(i)
-                    if isinstance(f, frames_mod.Nv12Frame):
+                    if isinstance(f, frames_hdr.HdrFrame):
+                        hdr.append((f, imgs[i].ptr))
+                    elif isinstance(f, frames_mod.Nv12Frame):
                         if not f.is_device:
                             f = frames_mod.stage_nv12(self._h2d, f, self._ctx.scratch(f"frame{i}_nv12",
                                                                                       f.packed_bytes).ptr,
@@ -939,6 +950,7 @@ class FaceEmbedder(YoloFaceBranch):
                         self._h2d.stage_frame(f, imgs[i].ptr, self._stage_threads)
                 self._ctx.wait_fence(self._h2d.fence(f"h2d{ci % 4}"))
                 frames_mod.convert_on_device(self._ctx, nv12)
+                self._hdr.convert(hdr)
             by_dyn: Dict[int, List[int]] = {}
             for i in chunks[ci]:
                 if spec_dyn[i] is not None:

@@ -25,7 +25,8 @@ A sample may arrive as a frames.Nv12Frame (the reference's NV12 pipe format, vid
 it is uploaded as NV12 and converted on the device. With PERSON_CAPTURE_AMD_NV12_FUSED=1 a sample wider
 than `prescan_max_width` goes through the fused conversion + INTER_AREA downscale
 (pc_nv12_resize_area_batch) instead, and its full-size BGR frame is never written; the bytes are the
-same either way (DESIGN.md §12 has the measurement behind the default).
+same either way (DESIGN.md §12 has the measurement behind the default). A frames_hdr.HdrFrame (the float32
+HDR pipe format) is converted on the device (pc_hdr_to_bgr) and then takes the BGR downscale.
 
 Not here (GUI/IO plumbing outside the per-frame hot path): the command queue (pause, seek,
 step, live cfg edits), decoder seeking, previews and progress signals, and the edge
@@ -40,6 +41,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .frames import Nv12Frame
+from .frames_hdr import HdrFrame
 from .match import fd_min, stream_ref_bank_update
 
 
@@ -263,6 +265,8 @@ class PrescanRunner:
         if isinstance(im, Nv12Frame):
             if self.nv12_fused and im.W > int(self.cfg.prescan_max_width):
                 return self.face._upload_nv12_planes(im, key + "_nv12")
+            return self.face._upload(im, key=key)
+        if isinstance(im, HdrFrame):   # converted (two source scratch buffers, frames_hdr.HdrStager), then resized
             return self.face._upload(im, key=key)
         return self.face._upload(np.ascontiguousarray(im), key=key)
 
