@@ -61,6 +61,15 @@
  *                                      (utils.py:152-196), batched; the host finishes them
  *   pc_sim_matrix                      Fs @ Fs.T of Curator.select (dataset_curator.py:961-977)
  *   pc_mmr_order                       mmr_select_with_q (dataset_curator.py:211-238)
+ *   pc_frame_gray                      Processor.run's per-frame cv2.cvtColor(frame, BGR2GRAY) (gui_app.py:5754,
+ *                                      3425) and the row / column means of detect_black_borders
+ *                                      (utils.py:152-196) behind _autocrop_borders (gui_app.py:3360-3384)
+ *   pc_gray_region_hist                the strip statistics of _is_real_letterbox_crop (gui_app.py:3429-3447):
+ *                                      np.percentile 95 / 99 and np.std, finished on the host from exact counts
+ *   pc_gray_motion                     absdiff + threshold(15) + countNonZero of _faceless_validate
+ *                                      (gui_app.py:4275-4285), all boxes of a frame at once
+ *   pc_gray_resize_area                cv2.resize(gray, (small_w, small_h), INTER_AREA) of _smart_crop_box's
+ *                                      gradient saliency (gui_app.py:8295-8301)
  */
 #ifndef PCGPU_H
 #define PCGPU_H
@@ -240,6 +249,39 @@ typedef struct pc_curate_record {
   uint32_t hist[256]; /* of the full-size gray plane */
   float coef[64];     /* [u][v] 8x8 low-frequency block of the orthonormal DCT-II of the 32 x 32 plane */
 } pc_curate_record;
+
+/* One frame of pc_frame_gray: a BGR u8 image on the device (32 <= w, h <= PC_GAUGE_MAX_SIDE, rows row_stride
+ * >= 3 w bytes apart) and where its results go: the gray plane (h rows of gray_pitch bytes; pointer and pitch
+ * multiples of 16, gray_pitch >= w rounded up to 16: the bytes of a row from w to that multiple are written as
+ * 0), row_sum[h] and col_sum[w] (u32, 4-byte aligned). */
+typedef struct pc_gray_desc {
+  const uint8_t* d_src;
+  int32_t row_stride, w, h;
+  int32_t gray_pitch;
+  uint8_t* d_gray;
+  uint32_t* d_row_sum;
+  uint32_t* d_col_sum;
+} pc_gray_desc;
+#define PC_GAUGE_MAX_SIDE 16384
+
+/* One rectangle of pc_gray_region_hist: columns [x, x + w), rows [y, y + h) of a u8 plane whose rows are
+ * pitch bytes apart. 1 <= w, h <= PC_GAUGE_MAX_SIDE, 0 <= x, y, x + w <= pitch <= PC_GAUGE_MAX_PITCH,
+ * y + h <= PC_GAUGE_MAX_SIDE (the caller answers for the plane having that many rows). */
+typedef struct pc_gray_region {
+  const uint8_t* d_plane;
+  int32_t pitch, x, y, w, h;
+  int32_t pad_;
+} pc_gray_region;
+#define PC_GAUGE_MAX_PITCH (1 << 20)
+
+/* One box of pc_gray_motion: columns [x1, x2), rows [y1, y2) of two u8 planes of the same pitch.
+ * 0 <= x1 < x2 <= pitch <= PC_GAUGE_MAX_PITCH, 0 <= y1 < y2 <= PC_GAUGE_MAX_SIDE, x2 - x1 <= PC_GAUGE_MAX_SIDE. */
+typedef struct pc_motion_box {
+  const uint8_t* d_cur;
+  const uint8_t* d_prev;
+  int32_t pitch, x1, y1, x2, y2;
+  int32_t pad_;
+} pc_motion_box;
 
 int pc_abi_version(void);
 
@@ -509,6 +551,42 @@ int pc_sim_matrix(pc_ctx* ctx, const float* d_F, int n, int dim, float* d_S);
  * d_order [k] i32; score = alpha q - (1 - alpha) max(0, max over picked S) in f64, greatest first,
  * lowest index on ties. 1 <= k <= n <= 8192. */
 int pc_mmr_order(pc_ctx* ctx, const float* d_S, const float* d_q, int n, int k, double alpha, int32_t* d_order);
+
+/* ---- main-pass frame gauges (Processor.run's gray-plane measurements, gui_app.py:5740-8002) ---- */
+/* cv2.cvtColor(frame, BGR2GRAY) of every processed frame (gui_app.py:5754; the second one of
+ * _is_real_letterbox_crop, gui_app.py:3425, is the same plane) for n frames of any mix of sizes in one
+ * launch, with the row and column sums of the plane that detect_black_borders (utils.py:152-196, called at
+ * gui_app.py:3370) turns into means. The 14-bit-coefficient arithmetic of pc_face_quality and
+ * pc_crop_metrics; none of the latter's resized planes, Laplacian or DCT. The sums are zeroed here. Nothing
+ * outside [row, row + 3 w) of a source row is read. n == 0: PC_OK, nothing enqueued. n < 0, a null or
+ * misaligned pointer, a side outside [32, PC_GAUGE_MAX_SIDE], row_stride < 3 w, or a gray_pitch that is no
+ * multiple of 16 or smaller than w rounded up to 16: PC_ERR_ARG before anything is staged or enqueued,
+ * whichever frame of the batch is the bad one. */
+int pc_frame_gray(pc_ctx* ctx, const pc_gray_desc* h_descs, int n);
+/* Exact 256-bin histograms of n rectangles of gray planes, d_out [n][256] u32 (zeroed here), in one launch:
+ * what _is_real_letterbox_crop's _strip_ok (gui_app.py:3429-3447) sorts twice per strip for
+ * np.percentile(., 95), np.percentile(., 99) and np.std; the host derives all three from the counts.
+ * Rectangles may overlap (the four strips of a frame share its corners); each is counted in full. Row
+ * segments move 16 bytes per load where they are aligned, byte by byte in their heads, tails and in strips
+ * narrower than that; no byte outside [x, x + w) of a row is read. n == 0: PC_OK, nothing enqueued. n < 0 or
+ * > 65535, a null pointer, d_out not 4-byte aligned or a rectangle outside the limits of pc_gray_region:
+ * PC_ERR_ARG before anything is staged or enqueued. */
+int pc_gray_region_hist(pc_ctx* ctx, const pc_gray_region* h_regions, int n, uint32_t* d_out);
+/* cv2.absdiff + cv2.threshold(diff, thresh, 255, THRESH_BINARY) + cv2.countNonZero of _faceless_validate
+ * (gui_app.py:4277-4282, thresh 15) for n boxes in one launch: d_counts[i] (u32, zeroed here) = the pixels of
+ * box i with |cur - prev| > thresh, strictly. 0 <= thresh <= 255. n == 0: PC_OK, nothing enqueued. n < 0 or
+ * > 65535, a null pointer, d_counts not 4-byte aligned, thresh out of range or a box outside the limits of
+ * pc_motion_box: PC_ERR_ARG before anything is staged or enqueued. */
+int pc_gray_motion(pc_ctx* ctx, const pc_motion_box* h_boxes, int n, int thresh, uint32_t* d_counts);
+/* cv2.resize(gray, (ow, oh), INTER_AREA) of one w x h gray plane, the small plane of _smart_crop_box's
+ * gradient saliency (gui_app.py:8295-8301): kind PC_CURATE_FAST (integer ratios isx x isy, ow isx <= w,
+ * oh isy <= h; tables ignored) or PC_CURATE_AREA (tables as pc_resize_area, every source index checked
+ * against w, h), the one-channel arithmetic of pc_crop_metrics' planes. The identity (PC_CURATE_COPY) is
+ * the caller's: the plane is its own resize. 1 <= ow <= w, 1 <= oh <= h <= PC_GAUGE_MAX_SIDE, pitch >= w,
+ * dst_pitch >= ow; anything else PC_ERR_ARG before anything is staged or enqueued. */
+int pc_gray_resize_area(pc_ctx* ctx, const uint8_t* d_gray, int pitch, int w, int h, int kind, int isx, int isy,
+                        const pc_area_tab* h_xtab, const int32_t* h_xstart, int n_x, const pc_area_tab* h_ytab,
+                        const int32_t* h_ystart, int n_y, uint8_t* d_dst, int dst_pitch, int ow, int oh);
 
 /* ---- host-side align geometry (CPU, batched) ---- */
 /* cv::estimateAffinePartial2D(from, to, method=LMEDS) for n point sets of npts points each

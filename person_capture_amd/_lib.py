@@ -113,6 +113,25 @@ class CurateDesc(C.Structure):
 PC_CURATE_COPY, PC_CURATE_FAST, PC_CURATE_AREA = 0, 1, 2
 CURATE_RECORD_BYTES = 1312   # sizeof(pc_curate_record)
 
+class GrayDesc(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("row_stride", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("gray_pitch", C.c_int32), ("d_gray", C.c_void_p), ("d_row_sum", C.c_void_p),
+                ("d_col_sum", C.c_void_p)]
+
+
+class GrayRegion(C.Structure):
+    _fields_ = [("d_plane", C.c_void_p), ("pitch", C.c_int32), ("x", C.c_int32), ("y", C.c_int32),
+                ("w", C.c_int32), ("h", C.c_int32), ("pad_", C.c_int32)]
+
+
+class MotionBox(C.Structure):
+    _fields_ = [("d_cur", C.c_void_p), ("d_prev", C.c_void_p), ("pitch", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32), ("x2", C.c_int32), ("y2", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(GrayDesc) == 48 and C.sizeof(GrayRegion) == 32 and C.sizeof(MotionBox) == 40
+PC_GAUGE_MAX_SIDE = 16384
+
 assert C.sizeof(CurateDesc) == 72 and C.sizeof(ChipDesc) == 24
 assert C.sizeof(YoloLetterboxDesc) == 64 and C.sizeof(YoloScale) == 20 and C.sizeof(CropDesc) == 24
 assert C.sizeof(ResizeDesc) == 80 and C.sizeof(LetterboxDesc) == 56 and C.sizeof(WarpDesc) == 96 and C.sizeof(AreaTab) == 12
@@ -204,6 +223,11 @@ SIGNATURES = {
     "pc_crop_metrics": ([_P, C.POINTER(CurateDesc), _I, _P, _I, _P, _I, _P, _P, _SZ, _P, _SZ], _I),
     "pc_sim_matrix": ([_P, _P, _I, _I, _P], _I),
     "pc_mmr_order": ([_P, _P, _P, _I, _I, C.c_double, _P], _I),
+    "pc_frame_gray": ([_P, C.POINTER(GrayDesc), _I], _I),
+    "pc_gray_region_hist": ([_P, C.POINTER(GrayRegion), _I, _P], _I),
+    "pc_gray_motion": ([_P, C.POINTER(MotionBox), _I, _I, _P], _I),
+    "pc_gray_resize_area": ([_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(AreaTab), C.POINTER(C.c_int32), _I,
+                             C.POINTER(AreaTab), C.POINTER(C.c_int32), _I, _P, _I, _I, _I], _I),
 }
 
 

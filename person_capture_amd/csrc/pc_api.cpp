@@ -20,6 +20,7 @@
 #include "../../include/pcgpu.h"
 #include "pc_net_dev.h"
 #include "pc_curate.h"
+#include "pc_gauge.h"
 
 namespace pc {
 struct LetterboxDesc;
@@ -54,6 +55,13 @@ hipError_t curate_metrics_launch(const void* d_imgs, int n, const void* d_bands,
                                  const int* d_starts, const double* d_dct, int max_pixels, hipStream_t s);
 hipError_t sim_matrix_launch(const float* F, int n, int dim, float* S, hipStream_t s);
 hipError_t mmr_order_launch(const float* S, const float* q, int n, int k, double alpha, int* order, hipStream_t s);
+// pc_gauge.hip
+hipError_t frame_gray_launch(const void* d_imgs, const void* d_bands, int nbands, int band, hipStream_t s);
+hipError_t gauge_region_hist_launch(const void* d_regs, const void* d_jobs, int njobs, hipStream_t s);
+hipError_t gauge_motion_launch(const void* d_boxes, const void* d_jobs, int njobs, int thresh, hipStream_t s);
+hipError_t gauge_resize_launch(const uint8_t* gray, long long gpitch, int kind, int isx, int isy, const void* xt,
+                               const int* xs, const void* yt, const int* ys, uint8_t* dst, long long dpitch, int ow,
+                               int oh, hipStream_t s);
 hipError_t embed_finalize_launch(const float* e, int ld, int n, int dim, int flip, float* out, hipStream_t s);
 hipError_t bank_match_launch(const float* q, int n, const float* bank, int B, int dim, float* fd, int* idx,
                              hipStream_t s);
@@ -1324,5 +1332,185 @@ extern "C" int pc_mmr_order(pc_ctx* c, const float* S, const float* q, int n, in
   if (n == 0 || k == 0) return PC_OK;
   if (!S || !q || !order) return fail(c, PC_ERR_ARG, "pc_mmr_order: null argument");
   HIPCHK(c, mmr_order_launch(S, q, n, k, alpha, order, c->stream));
+  return PC_OK;
+}
+
+// ---- main-pass frame gauges (pc_gauge.hip) ----
+static_assert(sizeof(pc_gray_desc) == 48 && sizeof(pc_gray_region) == 32 && sizeof(pc_motion_box) == 40,
+              "gauge layouts");
+
+// the rows of `h` rows of U units each, cut into jobs of about GAUGE_JOB_UNITS units
+static void gauge_jobs(std::vector<GaugeJob>& jobs, int item, int w, int h) {
+  const int U = (w + 15) / 16 + 1;
+  const int rows = std::max(1, GAUGE_JOB_UNITS / U);
+  for (int y = 0; y < h; y += rows) jobs.push_back(GaugeJob{item, y, std::min(rows, h - y), 0});
+}
+
+extern "C" int pc_frame_gray(pc_ctx* c, const pc_gray_desc* h, int n) {
+  if (!c) return PC_ERR_ARG;
+  if (n < 0 || n > 65535 || (n > 0 && !h)) return fail(c, PC_ERR_ARG, "pc_frame_gray: bad arguments");
+  if (n == 0) return PC_OK;
+  std::vector<GaugeImg> imgs((size_t)n);
+  std::vector<int> bands;
+  for (int i = 0; i < n; ++i) {
+    const pc_gray_desc& q = h[i];
+    if (!q.d_src || !q.d_gray || !q.d_row_sum || !q.d_col_sum || q.w < 32 || q.h < 32 || q.w > PC_GAUGE_MAX_SIDE ||
+        q.h > PC_GAUGE_MAX_SIDE || (long long)q.row_stride < 3LL * q.w || (q.gray_pitch & 15) ||
+        q.gray_pitch < ((q.w + 15) & ~15) || ((uintptr_t)q.d_gray & 15) || ((uintptr_t)q.d_row_sum & 3) ||
+        ((uintptr_t)q.d_col_sum & 3))
+      return fail(c, PC_ERR_ARG, "pc_frame_gray: bad frame (non-null pointers, 32 <= w, h <= 16384, row_stride >= 3 w, "
+                                 "d_gray and gray_pitch multiples of 16, gray_pitch >= w rounded up to 16, "
+                                 "4-byte aligned sums)");
+    GaugeImg& m = imgs[i];
+    memset(&m, 0, sizeof(m));
+    m.src = q.d_src; m.row_stride = q.row_stride; m.w = q.w; m.h = q.h; m.gpitch = q.gray_pitch;
+    m.gray = q.d_gray; m.row_sum = q.d_row_sum; m.col_sum = q.d_col_sum;
+  }
+  // Rows per workgroup: the tallest band of 32, 16, 8 that still gives GAUGE_MIN_WG workgroups (four per CU;
+  // one 4K frame in bands of 32 would be 68 workgroups on 256 CUs), else 8. A shorter band costs one more
+  // column atomic per column and band, so it is not taken where the batch fills the device anyway.
+  int band = GAUGE_BAND;
+  for (; band > 8; band >>= 1) {
+    long long wg = 0;
+    for (int i = 0; i < n; ++i) wg += (h[i].h + band - 1) / band;
+    if (wg >= GAUGE_MIN_WG) break;
+  }
+  for (int i = 0; i < n; ++i)
+    for (int y = 0; y < h[i].h; y += band) { bands.push_back(i); bands.push_back(y); }
+  const size_t o_band = (imgs.size() * sizeof(GaugeImg) + 15) & ~size_t(15);
+  const size_t total = o_band + bands.size() * sizeof(int);
+  std::vector<char> blob(total, 0);
+  memcpy(blob.data(), imgs.data(), imgs.size() * sizeof(GaugeImg));
+  memcpy(blob.data() + o_band, bands.data(), bands.size() * sizeof(int));
+  void* dv = nullptr;
+  int rc = stage_copy(c, blob.data(), total, &dv);
+  if (rc) return rc;
+  // The column sums are accumulated: zero them. A frame whose row sums end where its column sums begin is
+  // zeroed as one span (the row sums are written in full afterwards), and spans that touch share a memset:
+  // frames laid out back to back cost one. Nothing between two spans is written.
+  auto span = [&](int i, char*& lo, char*& hi) {
+    lo = (char*)h[i].d_col_sum;
+    hi = lo + (size_t)h[i].w * 4;
+    if ((char*)(h[i].d_row_sum + h[i].h) == lo) lo = (char*)h[i].d_row_sum;
+  };
+  for (int i = 0; i < n;) {
+    char *lo, *hi;
+    span(i, lo, hi);
+    int j = i + 1;
+    for (; j < n; ++j) {
+      char *a, *b;
+      span(j, a, b);
+      if (a != hi) break;
+      hi = b;
+    }
+    HIPCHK(c, hipMemsetAsync(lo, 0, (size_t)(hi - lo), c->stream));
+    i = j;
+  }
+  HIPCHK(c, frame_gray_launch(dv, (char*)dv + o_band, (int)(bands.size() / 2), band, c->stream));
+  return PC_OK;
+}
+
+extern "C" int pc_gray_region_hist(pc_ctx* c, const pc_gray_region* h, int n, uint32_t* d_out) {
+  if (!c) return PC_ERR_ARG;
+  if (n < 0 || n > 65535 || (n > 0 && (!h || !d_out)) || ((uintptr_t)d_out & 3))
+    return fail(c, PC_ERR_ARG, "pc_gray_region_hist: bad arguments");
+  if (n == 0) return PC_OK;
+  std::vector<GaugeRegion> regs((size_t)n);
+  std::vector<GaugeJob> jobs;
+  for (int i = 0; i < n; ++i) {
+    const pc_gray_region& q = h[i];
+    if (!q.d_plane || q.w < 1 || q.h < 1 || q.w > PC_GAUGE_MAX_SIDE || q.h > PC_GAUGE_MAX_SIDE || q.x < 0 || q.y < 0 ||
+        q.pitch > PC_GAUGE_MAX_PITCH || (long long)q.x + q.w > q.pitch || (long long)q.y + q.h > PC_GAUGE_MAX_SIDE)
+      return fail(c, PC_ERR_ARG, "pc_gray_region_hist: bad region (non-null plane, 1 <= w, h <= 16384, 0 <= x, y, "
+                                 "x + w <= pitch <= 2^20, y + h <= 16384)");
+    GaugeRegion& r = regs[i];
+    memset(&r, 0, sizeof(r));
+    r.base = q.d_plane + (long long)q.y * q.pitch + q.x;
+    r.pitch = q.pitch; r.w = q.w; r.h = q.h;
+    r.hist = d_out + (size_t)i * 256;
+    gauge_jobs(jobs, i, q.w, q.h);
+  }
+  const size_t o_job = (regs.size() * sizeof(GaugeRegion) + 15) & ~size_t(15);
+  const size_t total = o_job + jobs.size() * sizeof(GaugeJob);
+  std::vector<char> blob(total, 0);
+  memcpy(blob.data(), regs.data(), regs.size() * sizeof(GaugeRegion));
+  memcpy(blob.data() + o_job, jobs.data(), jobs.size() * sizeof(GaugeJob));
+  void* dv = nullptr;
+  int rc = stage_copy(c, blob.data(), total, &dv);
+  if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)n * 256 * sizeof(uint32_t), c->stream));
+  HIPCHK(c, gauge_region_hist_launch(dv, (char*)dv + o_job, (int)jobs.size(), c->stream));
+  return PC_OK;
+}
+
+extern "C" int pc_gray_motion(pc_ctx* c, const pc_motion_box* h, int n, int thresh, uint32_t* d_counts) {
+  if (!c) return PC_ERR_ARG;
+  if (n < 0 || n > 65535 || (n > 0 && (!h || !d_counts)) || ((uintptr_t)d_counts & 3) || thresh < 0 || thresh > 255)
+    return fail(c, PC_ERR_ARG, "pc_gray_motion: bad arguments (0 <= n <= 65535, 0 <= thresh <= 255)");
+  if (n == 0) return PC_OK;
+  std::vector<GaugeBox> boxes((size_t)n);
+  std::vector<GaugeJob> jobs;
+  for (int i = 0; i < n; ++i) {
+    const pc_motion_box& q = h[i];
+    if (!q.d_cur || !q.d_prev || q.x1 < 0 || q.y1 < 0 || q.x2 <= q.x1 || q.y2 <= q.y1 || q.pitch > PC_GAUGE_MAX_PITCH ||
+        q.x2 > q.pitch || q.y2 > PC_GAUGE_MAX_SIDE || q.x2 - q.x1 > PC_GAUGE_MAX_SIDE)
+      return fail(c, PC_ERR_ARG, "pc_gray_motion: bad box (non-null planes, 0 <= x1 < x2 <= pitch <= 2^20, "
+                                 "0 <= y1 < y2 <= 16384, x2 - x1 <= 16384)");
+    GaugeBox& b = boxes[i];
+    memset(&b, 0, sizeof(b));
+    const long long off = (long long)q.y1 * q.pitch + q.x1;
+    b.cur = q.d_cur + off; b.prev = q.d_prev + off;
+    b.pitch = q.pitch; b.w = q.x2 - q.x1; b.h = q.y2 - q.y1;
+    b.count = d_counts + i;
+    gauge_jobs(jobs, i, b.w, b.h);
+  }
+  const size_t o_job = (boxes.size() * sizeof(GaugeBox) + 15) & ~size_t(15);
+  const size_t total = o_job + jobs.size() * sizeof(GaugeJob);
+  std::vector<char> blob(total, 0);
+  memcpy(blob.data(), boxes.data(), boxes.size() * sizeof(GaugeBox));
+  memcpy(blob.data() + o_job, jobs.data(), jobs.size() * sizeof(GaugeJob));
+  void* dv = nullptr;
+  int rc = stage_copy(c, blob.data(), total, &dv);
+  if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)n * sizeof(uint32_t), c->stream));
+  HIPCHK(c, gauge_motion_launch(dv, (char*)dv + o_job, (int)jobs.size(), thresh, c->stream));
+  return PC_OK;
+}
+
+extern "C" int pc_gray_resize_area(pc_ctx* c, const uint8_t* d_gray, int pitch, int w, int h, int kind, int isx, int isy,
+                                   const pc_area_tab* xt, const int32_t* xs, int n_x, const pc_area_tab* yt,
+                                   const int32_t* ys, int n_y, uint8_t* d_dst, int dst_pitch, int ow, int oh) {
+  if (!c) return PC_ERR_ARG;
+  if (!d_gray || !d_dst || w < 1 || h < 1 || w > PC_GAUGE_MAX_SIDE || h > PC_GAUGE_MAX_SIDE || pitch < w || ow < 1 ||
+      oh < 1 || ow > w || oh > h || dst_pitch < ow)
+    return fail(c, PC_ERR_ARG, "pc_gray_resize_area: bad arguments (1 <= ow <= w <= pitch, 1 <= oh <= h <= 16384, "
+                               "dst_pitch >= ow)");
+  if (kind == PC_CURATE_FAST) {
+    if (isx < 1 || isy < 1 || (long long)ow * isx > w || (long long)oh * isy > h)
+      return fail(c, PC_ERR_ARG, "pc_gray_resize_area: integer ratios outside the plane");
+    HIPCHK(c, gauge_resize_launch(d_gray, pitch, 1, isx, isy, nullptr, nullptr, nullptr, nullptr, d_dst, dst_pitch, ow, oh,
+                                  c->stream));
+    return PC_OK;
+  }
+  if (kind != PC_CURATE_AREA) return fail(c, PC_ERR_ARG, "pc_gray_resize_area: kind is PC_CURATE_FAST or PC_CURATE_AREA");
+  if (!xt || !xs || !yt || !ys || n_x <= 0 || n_y <= 0 || !area_table_ok(xt, n_x, xs, ow, w) ||
+      !area_table_ok(yt, n_y, ys, oh, h))
+    return fail(c, PC_ERR_ARG, "pc_gray_resize_area: INTER_AREA tables out of range");
+  auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+  const size_t o_xs = up16((size_t)n_x * sizeof(pc_area_tab));
+  const size_t o_yt = up16(o_xs + (size_t)(ow + 1) * sizeof(int32_t));
+  const size_t o_ys = up16(o_yt + (size_t)n_y * sizeof(pc_area_tab));
+  const size_t total = o_ys + (size_t)(oh + 1) * sizeof(int32_t);
+  std::vector<char> blob(total, 0);
+  memcpy(blob.data(), xt, (size_t)n_x * sizeof(pc_area_tab));
+  memcpy(blob.data() + o_xs, xs, (size_t)(ow + 1) * sizeof(int32_t));
+  memcpy(blob.data() + o_yt, yt, (size_t)n_y * sizeof(pc_area_tab));
+  memcpy(blob.data() + o_ys, ys, (size_t)(oh + 1) * sizeof(int32_t));
+  void* dv = nullptr;
+  int rc = stage_copy(c, blob.data(), total, &dv);
+  if (rc) return rc;
+  char* db = (char*)dv;
+  HIPCHK(c, gauge_resize_launch(d_gray, pitch, 2, 0, 0, db, (const int*)(db + o_xs), db + o_yt, (const int*)(db + o_ys),
+                                d_dst, dst_pitch, ow, oh, c->stream));
   return PC_OK;
 }

@@ -25,6 +25,7 @@
 
 #include "pc_area.h"
 #include "pc_curate.h"
+#include "pc_gray.h"
 
 namespace pc {
 
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void curate_gray(const CurateImg* __restrict__
         union { uint4 v; uint8_t b[16]; } out;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int g = ((int)in.b[i * 3] * 1868 + (int)in.b[i * 3 + 1] * 9617 + (int)in.b[i * 3 + 2] * 4899 + (1 << 13)) >> 14;
+          const int g = gray14(in.b[i * 3], in.b[i * 3 + 1], in.b[i * 3 + 2]);
           out.b[i] = (uint8_t)g;
           if (i < nv) {
             col[i] += (unsigned)g;

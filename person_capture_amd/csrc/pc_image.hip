@@ -21,6 +21,7 @@
 #pragma clang fp contract(off)
 
 #include "pc_area.h"
+#include "pc_gray.h"
 
 namespace pc {
 
@@ -291,7 +292,7 @@ __global__ __launch_bounds__(1024) void face_quality(const uint8_t* __restrict__
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const int b = raw[i * 3 + 0], gg = raw[i * 3 + 1], r = raw[i * 3 + 2];
-    g[i] = (uint8_t)((b * 1868 + gg * 9617 + r * 4899 + (1 << 13)) >> 14);
+    g[i] = (uint8_t)gray14(b, gg, r);
   }
   __syncthreads();
   long long s1 = 0, s2 = 0;
