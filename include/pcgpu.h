@@ -470,6 +470,10 @@ int pc_embed_finalize(pc_ctx* ctx, const float* d_e, int ld, int n, int dim, int
 /* chips: [n][side][side][3] BGR u8 (side == net input side). d_feat: [n][dim] unit f32. A net whose
  * program flags a centred input (f16x3 IResNet) gets the PC_PREC_F16X3 preprocessing. */
 int pc_arcface_embed(pc_net* net, const uint8_t* d_chips, int n, int flip, float* d_feat);
+/* Processor._fd_min for n query rows d_q [n][dim] against d_bank [b][dim] unit rows: each query is divided
+ * by max(||q||, 1e-6), d_fd[i] = 1 - max_r dot(bank[r], q_i), d_idx[i] (may be null) the first row that
+ * reaches the maximum. An empty bank (b == 0; d_bank is not read) gives d_fd[i] = 9.0 and d_idx[i] = -1.
+ * dim % 64 != 0 or dim > 1024: PC_ERR_HIP, nothing enqueued (pc_embed_finalize and pc_l2_normalize too). */
 int pc_bank_match(pc_ctx* ctx, const float* d_q, int n, const float* d_bank, int b, int dim, float* d_fd,
                   int32_t* d_idx);
 
