@@ -327,6 +327,27 @@ int pc_fence_wait(pc_ctx* ctx, void* fence);
 int pc_fence_destroy(pc_ctx* ctx, void* fence);
 
 /* ---- networks (serialized program produced by person_capture_amd.netdef) ---- */
+/* pc_net_create and pc_net_plan decode and validate the program first (csrc/pc_program.cpp) and refuse, with
+ * PC_ERR_FORMAT and a message that names the op kind and the rule (pc_last_error / pc_net_plan's err), before
+ * anything is allocated or launched:
+ *   ids       a tensor, buffer or array id outside its table; an unknown op kind; a truncated table
+ *   tensors   H, W or C below 1; a channel slice [coff, coff + C) outside the pixel stride cs; H * W * cs
+ *             beyond the tensor's buffer; is_f32 unlike its buffer's; split / f16c8 storage rules
+ *   element   a max pool, upsample, LayerNorm or attention that reads or writes, or a stem that reads, an
+ *   type      is_f32 tensor of an f16 net (those kernels move the net's own type)
+ *   max pool  k < 1, stride < 1, pad outside [0, k / 2]; an output that is not (H + 2 pad - k) / stride + 1 in
+ *             each direction; channels unlike the input's; C, cs or coff no multiple of 4
+ *   upsample  an output that is not exactly twice the input; min(C), cs or coff no whole 16-byte vectors
+ *   LayerNorm C outside [1, 2048], wider than its input or output (the halves of split tensors), an output
+ *             wider than 2048; pixel counts that differ; gamma or beta shorter than C; a positional table
+ *             whose rows are not the pixels of an image or whose array is shorter than rows * C
+ *   attention a head dim other than 64 / 80; 3 * heads * d wider than qkv or heads * d wider than the output
+ *             (halves); token counts that differ; qkv cs no multiple of 8, output cs no multiple of 4 (f32)
+ *             or 8; an offset not aligned to 16 bytes
+ *   conv      1 or 2 segments; an output size that does not follow from every segment's window; a same-size
+ *             residual of another size, an upsampled one that is not half the output rounded up; weights
+ *             shorter than npad * ktot, bias shorter than npad (9 * npad in border mode), slopes than npad
+ * A net that is created is runnable: no shape rule is left to fail as a launch error. */
 int pc_net_create(pc_ctx* ctx, const void* h_program, size_t program_bytes, int precision, int max_batch,
                   pc_net** out);
 int pc_net_destroy(pc_net* net);

@@ -103,8 +103,17 @@ struct NetDesc {
 // from there, so the tail covers the widest pixel row a conv reads.
 static const size_t kZeroTail = 65536;
 
-// Parses and validates a program: PC_OK, or PC_ERR_FORMAT / PC_ERR_ARG with a message in err. After it
-// every tensor, buffer and array id of every op indexes its table.
+// Parses and validates a program: PC_OK, or PC_ERR_FORMAT / PC_ERR_ARG with a message in err that names the op
+// kind and the rule. "Validated" covers, after it returns PC_OK:
+//  * ids: every tensor, buffer and array id of every op indexes its table;
+//  * tensors (check_tensor): H, W, C >= 1, the channel slice inside the pixel stride, every pixel inside the
+//    buffer, is_f32 as the buffer's; the split / f16c8 storage rules;
+//  * geometry (check_geometry): what each kernel's own indexing assumes - the pool and conv output sizes, the
+//    doubled upsample, LayerNorm's C against both tensors, its arrays and the kernel's 2048-channel limit,
+//    attention's widths, token counts and 16-byte alignment, residual sizes, array lengths, and the element
+//    type the non-GEMM kernels and the stem move (include/pcgpu.h lists the refusals).
+// So a decoded program reads and writes inside its tensors and arrays. What the planner still decides (tile
+// fits, split-K, which conv family can take a layer) is plan_net's, with its own PC_ERR_FORMAT messages.
 int decode_program(const void* prog, size_t nbytes, int precision, int max_batch, NetDesc& d, std::string& err);
 template <typename F>
 static inline void for_each_input(const NetOp& op, F&& fn) {   // the tensors an op reads

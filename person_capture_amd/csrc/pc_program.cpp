@@ -2,6 +2,7 @@
 // code that reads op records by word position (pc_net.h OpWord); everything after it works on the typed ops
 // and may index the tensor, buffer and array tables with any id it finds there.
 #include <string.h>
+#include <algorithm>
 #include "pc_net.h"
 
 namespace pc {
@@ -79,6 +80,95 @@ struct Decoder {
     }
   }
 };
+
+// Every tensor lies inside its buffer: a pixel holds its channel slice, the buffer holds every pixel,
+// and tensor and buffer agree on the element type. (buf -1: the net input, the caller's memory.)
+const char* check_tensor(const NetDesc& d, const NetTensor& t) {
+  if (t.buf < -1) return "malformed program: tensor: buffer id out of range";
+  if (t.H < 1 || t.W < 1 || t.C < 1) return "malformed program: tensor: H, W and C must be at least 1";
+  if (t.coff < 0 || (long long)t.coff + t.C > t.cs) return "malformed program: tensor: channel slice [coff, coff + C) outside the pixel stride";
+  if (t.buf >= 0) {
+    const NetBuf& b = d.bufs[t.buf];
+    if ((long long)t.H * t.W * t.cs > b.elems) return "malformed program: tensor: larger than its buffer";
+    if ((t.is_f32 != 0) != (b.is_f32 != 0)) return "malformed program: tensor: is_f32 differs from its buffer's";
+  }
+  return nullptr;
+}
+
+// The shape rules of every op, from the kernels' own indexing (pc_conv.hip max pools, pc_ops.hip, pc_attn.hip,
+// pc_conv_common.h epilogue): a program that passes reads and writes inside its tensors. nullptr: fine.
+const char* check_geometry(const NetDesc& d, const NetOp& op) {
+  const int k = op.kind;
+  auto cnt = [&](int a) { return d.arrays[a].cnt; };
+  // the window's output size, in 64 bits (every operand comes from the file); -1: the window does not fit
+  auto out_dim = [](long long in, long long win, long long stride, long long pad) {
+    return in + 2 * pad < win ? -1LL : (in + 2 * pad - win) / stride + 1;
+  };
+  const NetTensor& Y = d.tens[op.out()];
+  if (k == OP_CONV) {
+    const ConvOp& c = op.conv;
+    for (int s = 0; s < c.nseg; ++s) {
+      const ConvSegOp& g = c.seg[s];
+      const NetTensor& X = d.tens[g.x];
+      if (Y.H != out_dim(X.H, g.KH, g.stride, g.pad) || Y.W != out_dim(X.W, g.KW, g.stride, g.pad))
+        return "conv: the output size does not follow from a segment's input and window";
+    }
+    if (c.res >= 0) {
+      const NetTensor& R = d.tens[c.res];
+      if (c.res_mode == RES_SAME && (R.H != Y.H || R.W != Y.W)) return "conv: a same-size residual must have the output's size";
+      // the epilogue reads residual pixel (oh >> 1, ow >> 1)
+      if (c.res_mode == RES_UP2 && (R.H != ((long long)Y.H + 1) / 2 || R.W != ((long long)Y.W + 1) / 2))
+        return "conv: an upsampled residual must have half the output's size, rounded up";
+      if (c.res_mode != RES_SAME && c.res_mode != RES_UP2) return "conv: the residual mode must be same-size (1) or upsampled (2)";
+    }
+    if (cnt(c.w) < (long long)c.npad * c.ktot) return "conv: the weight array holds fewer than npad * ktot floats";
+    if (c.bias >= 0 && cnt(c.bias) < (long long)c.npad * (c.bias_mode == BIAS_BORDER9 ? 9 : 1))
+      return "conv: the bias array holds fewer than npad floats (9 * npad in border mode)";
+    if (c.slope >= 0 && cnt(c.slope) < c.npad) return "conv: the slope array holds fewer than npad floats";
+    return nullptr;
+  }
+  const NetTensor& X = d.tens[op.io.x];
+  // the stem and the four non-GEMM kernels read and write the net's own element type
+  if (!d.f32 && (X.is_f32 || (k != OP_STEM && Y.is_f32))) {
+    switch (k) {
+      case OP_STEM: return "stem: reads the net's element type, not an is_f32 tensor of an f16 net";
+      case OP_MAXPOOL: return "max pool: reads and writes the net's element type, not an is_f32 tensor of an f16 net";
+      case OP_UPSAMPLE: return "upsample: reads and writes the net's element type, not an is_f32 tensor of an f16 net";
+      case OP_LAYERNORM: return "layernorm: reads and writes the net's element type, not an is_f32 tensor of an f16 net";
+      default: return "attention: reads and writes the net's element type, not an is_f32 tensor of an f16 net";
+    }
+  }
+  const int xc = X.split ? X.C / 2 : X.C, yc = Y.split ? Y.C / 2 : Y.C;   // logical widths
+  const int V = d.f32 ? 4 : 8;                                            // elements of a 16-byte vector
+  if (k == OP_MAXPOOL) {
+    const PoolOp& p = op.pool;
+    if (p.k < 1 || p.stride < 1 || p.pad < 0 || p.pad > p.k / 2) return "max pool: window needs k >= 1, stride >= 1 and 0 <= pad <= k / 2";
+    if (Y.H != out_dim(X.H, p.k, p.stride, p.pad) || Y.W != out_dim(X.W, p.k, p.stride, p.pad))
+      return "max pool: the output size does not follow from the input and the window";
+    if (Y.C != X.C) return "max pool: input and output must have the same channels";
+    if (xc % 4 || X.cs % 4 || Y.cs % 4 || X.coff % 4 || Y.coff % 4) return "max pool: channels, pixel strides and offsets must be multiples of 4";
+  } else if (k == OP_UPSAMPLE) {
+    if (Y.H != 2LL * X.H || Y.W != 2LL * X.W) return "upsample: the output must be twice the input's height and width";
+    if (std::min(X.C, Y.C) % V || X.cs % V || Y.cs % V || X.coff % V || Y.coff % V)
+      return "upsample: channels, pixel strides and offsets must be whole 16-byte vectors";
+  } else if (k == OP_LAYERNORM) {
+    const LayerNormOp& l = op.ln;
+    if (l.C < 1 || l.C > 2048 || yc > 2048) return "layernorm: 1 <= C <= 2048 and an output of at most 2048 channels";
+    if (l.C > xc || l.C > yc) return "layernorm: C wider than its input or output tensor";
+    if ((long long)X.H * X.W != (long long)Y.H * Y.W) return "layernorm: input and output must have the same pixels";
+    if (cnt(l.gamma) < l.C || cnt(l.beta) < l.C) return "layernorm: gamma and beta must hold C floats";
+    if (l.add >= 0 && (l.rows < 1 || l.rows != (long long)X.H * X.W || cnt(l.add) < (long long)l.rows * l.C))
+      return "layernorm: the positional table must hold one row of C floats per pixel of an image";
+  } else if (k == OP_ATTENTION) {
+    const AttnOp& a = op.attn;
+    const long long E = (long long)a.heads * a.head_dim;
+    if (3 * E > xc || E > yc) return "attention: 3 * heads * d wider than the qkv tensor, or heads * d wider than the output";
+    if ((long long)X.H * X.W != (long long)Y.H * Y.W) return "attention: input and output must have the same tokens";
+    if (X.cs % 8 || Y.cs % V) return "attention: pixel strides must be multiples of 8 (qkv) and of 4 (f32) or 8 (f16) elements (output)";
+    if (X.coff % V || Y.coff % V) return "attention: tensor offsets must be aligned to 16 bytes";
+  }
+  return nullptr;
+}
 }  // namespace
 
 int decode_program(const void* prog, size_t nbytes, int precision, int max_batch, NetDesc& d, std::string& err) {
@@ -118,6 +208,10 @@ int decode_program(const void* prog, size_t nbytes, int precision, int max_batch
     if (o < 0 || o >= nten) return fail(PC_ERR_FORMAT, "malformed program: output tensor id out of range");
   for (const NetArray& a : d.arrays)
     if (a.off < 0 || a.cnt < 0 || (size_t)(a.off + a.cnt) > d.ndata) return fail(PC_ERR_FORMAT, "array out of range");
+  for (const NetBuf& b : d.bufs)
+    if (b.elems < 0) return fail(PC_ERR_FORMAT, "malformed program: buffer size");
+  for (const NetTensor& t : d.tens)
+    if (const char* why = check_tensor(d, t)) return fail(PC_ERR_FORMAT, why);
   Decoder dec{d, err};
   d.ops.resize(nop);
   for (int i = 0; i < nop; ++i)
@@ -155,6 +249,8 @@ int decode_program(const void* prog, size_t nbytes, int precision, int max_batch
   }
   for (auto& op : d.ops)
     if (op.kind == OP_STEM && d.tens[op.stem.x].split) return fail(PC_ERR_FORMAT, "op cannot read or write split tensors");
+  for (auto& op : d.ops)
+    if (const char* why = check_geometry(d, op)) return fail(PC_ERR_FORMAT, why);
   return PC_OK;
 }
 

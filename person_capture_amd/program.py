@@ -34,7 +34,8 @@ Binary format (little-endian int32 words, then float32 data):
                          [7] eps (f32 bits)  [8] channels
               ATTENTION  [2] qkv  [3] heads  [4] head dim
             Tensor and array ids must index their tables (-1 only where "none" is allowed): a program that
-            breaks this is refused with PC_ERR_FORMAT.
+            breaks this is refused with PC_ERR_FORMAT, and so is one whose tensors do not fit their buffers or
+            whose op geometry a kernel would follow outside its tensors (include/pcgpu.h lists the rules).
   data    : float32
 """
 from __future__ import annotations

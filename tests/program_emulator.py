@@ -59,14 +59,17 @@ def run_program(P: pg.Program, x_nhwc: np.ndarray):
         vb, H, W, C, cs, off, _ = P.tensors[t]
         if vb not in bufs:
             bufs[vb] = torch.zeros(N, cs, H, W)
+        # (an op may write fewer channels than the tensor holds: attention writes heads * d)
         if tsplit[t]:   # device epilogue: hi = f16(v), lo = f16(v - hi)
             h = C // 2
-            v = y[:, :h].float()
+            k = min(h, y.shape[1])
+            v = y[:, :k].float()
             hi = v.half().float()
-            bufs[vb][:, off:off + h] = hi
-            bufs[vb][:, off + h:off + C] = (v - hi).half().float()
+            bufs[vb][:, off:off + k] = hi
+            bufs[vb][:, off + h:off + h + k] = (v - hi).half().float()
             return
-        bufs[vb][:, off:off + C] = y[:, :C]
+        k = min(C, y.shape[1])
+        bufs[vb][:, off:off + k] = y[:, :k]
 
     def logical_c(t):
         C = P.tensors[t][3]

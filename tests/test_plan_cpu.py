@@ -12,6 +12,8 @@ import pytest
 from person_capture_amd import _lib, models
 from person_capture_amd import program as pg
 from person_capture_amd._lib import PC_PREC_F16
+from plan_geometry_cases import geometry_cases as _geometry_cases
+from plan_geometry_cases import valid_geometry_programs as _valid_geometry_programs
 
 PC_ERR_FORMAT = 4   # pcgpu.h
 KIND, CODE, FORM, ROWB, SPLITK, CFG = range(6)
@@ -103,6 +105,66 @@ def test_malformed_program_is_refused(name):
     k, msg = _plan(_malformed_cases()[name], 8)
     assert k == -PC_ERR_FORMAT, (k, msg)
     assert msg
+
+
+# ---- geometry the kernels would follow outside their tensors (plan_geometry_cases.py) ---------------
+@pytest.mark.parametrize("name", sorted(_valid_geometry_programs()))
+def test_geometry_bases_plan(name):
+    """The programs the geometry cases below are cut from are themselves accepted."""
+    r = _plan(_valid_geometry_programs()[name].serialize(), 4)
+    assert not isinstance(r[0], int), r
+
+
+@pytest.mark.parametrize("name", sorted(_geometry_cases()))
+def test_bad_geometry_is_refused(name):
+    P, words = _geometry_cases()[name]
+    k, msg = _plan(P.serialize(), 4)
+    assert k == -PC_ERR_FORMAT, (k, msg)
+    assert msg and words in msg, msg
+
+
+# ---- every program the project compiles is accepted --------------------------------------------------
+def _project_programs():
+    """(name, build) of every compiler's programs, synthetic weights: plain / split / c8 where the family has
+    them, and the op-level programs of net_op_cases.py. Built on demand (the towers' weights are large)."""
+    from person_capture_amd import models_clip as mc
+    from person_capture_amd import models_yolo as my
+    out = []
+    for depth in (18, 50, 100):
+        for kw in ({}, {"split": True}, {"c8": True}):
+            out.append((f"iresnet{depth}-{'-'.join(kw) or 'plain'}",
+                        lambda depth=depth, kw=kw: models.compile_iresnet(models.synth_iresnet(depth, seed=0, calibrate=False), depth, **kw)))
+    for v in ("2.5g", "10g"):
+        for D in (320, 640):
+            for split in (False, True):
+                out.append((f"scrfd{v}-{D}-{'split' if split else 'plain'}",
+                            lambda v=v, D=D, split=split: models.compile_scrfd(models.synth_scrfd(v, seed=0, calibrate=False), v, D, split=split)))
+    out.append(("yolov8n", lambda: my.compile_yolov8(my.synth_yolov8("n", seed=0, calibrate=False), "n", 384, 640)))
+    out.append(("yolov8n-face", lambda: my.compile_yolov8(my.synth_yolov8_face("n", seed=0, calibrate=False), "n", 384, 640,
+                                                          nc=1, kpt=(5, 3))))
+    for name in sorted(mc.CLIP_CFGS):
+        if mc.CLIP_CFGS[name]["layers"] > 2:
+            continue      # the family's full-depth rows: the -d2 rows are the same shapes per layer
+        for split in (False, True):
+            out.append((f"{name}-{'split' if split else 'plain'}",
+                        lambda name=name, split=split: mc.compile_clip_vit(mc.synth_clip_vit(name, seed=0), name, split=split)))
+    return out
+
+
+@pytest.mark.parametrize("name", [n for n, _ in _project_programs()])
+def test_every_compiled_program_plans(name):
+    P = dict(_project_programs())[name]()
+    precs = [PC_PREC_F16] if P.split else [PC_PREC_F16, _lib.PC_PREC_F32]
+    for prec in precs:
+        r = _plan(P.serialize(), 8, prec)
+        assert not isinstance(r[0], int), (name, prec, r)
+
+
+def test_every_op_level_program_plans():
+    import net_op_cases as nc
+    for case in nc.all_cases():
+        r = _plan(case.P.serialize(), 4, _lib.PC_PREC_F32 if case.f32 else PC_PREC_F16)
+        assert not isinstance(r[0], int), (case.name, r)
 
 
 def test_truncated_op_table_is_refused():
